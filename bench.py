@@ -11,12 +11,20 @@ carries merge_phases_ms, the shards' parity against the oracle's pass over the w
 a weak C2-per-rank sub-leg (`weak_c2`).  If RCCL cannot start on every rank the line fails (exit
 1, value null) -- no fallback transport is timed.
 
-Prints ONE JSON line (rank 0): value = frames integrated per second over all ranks, the mesh
-extraction time (weight_threshold 1.5, the pipeline's setting), the integrate kernel's roofline
-(algorithmic bytes per launch / its average HIP-event duration), the CPU-oracle baseline and the
-parity of the last timed step's volume, mesh and point cloud against the oracle's (checked before
-any other leg touches the volume).  The C4 (2000 frames L+R chained) and C5 (4000 frames @ 3 mm +
-colour) legs carry parity blocks of their own, on the volumes they timed.
+Prints ONE JSON line (rank 0).  A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints value = frames integrated per second over all ranks, ms_per_step and
+the integrate kernel's roofline (algorithmic bytes per launch / its average HIP-event duration over
+the timed steps themselves).  `--dump-outputs DIR` also writes the volume the last timed step left
+(dump_outputs).
+
+With `--full` the line also carries everything that takes runs of its own: the mesh extraction
+time (weight_threshold 1.5, the pipeline's setting), the touch launches' times, the CPU-oracle
+baseline and the parity of the last timed step's volume, mesh and point cloud against the oracle's
+(checked before any other leg touches the volume), the confidence / ingest / ray-cast / mesh-filter
+/ C3 / drop-in legs, and the C4 (2000 frames L+R chained) and C5 (4000 frames @ 3 mm + colour) legs
+with parity blocks of their own, on the volumes they timed; with N > 1 ranks the sharded
+extraction, its parity, the weak sub-leg and the sharded C5.  The --no-* switches and leg sizes
+below trim a `--full` run.
 """
 from __future__ import annotations
 
@@ -44,6 +52,12 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (extraction, touch timing, CPU baseline, "
+                         "parity, confidence / ingest / ray-cast / mesh-filter / C3 / C4 / C5 / drop-in; N > 1: "
+                         "sharded extraction, parity, weak sub-leg, sharded C5); off: the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's volume to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--frames", type=int, default=500)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
@@ -86,7 +100,12 @@ def parse(argv=None):
                     help="run only the C5 leg and print its record (rocprof of the peak-HBM run)")
     ap.add_argument("--launch-timeout", type=float, default=3000.0,
                     help="--gpus N > 1 without WORLD_SIZE: overall limit on the N self-launched ranks (s)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not (args.full or args.c5_only):
+        # a plain run: set up, warm up, time the steps, print the line -- no leg with runs of its own
+        args.no_cpu = args.no_parity = args.no_extras = args.no_c4 = args.no_c5 = True
+        args.extract_reps = args.touch_steps = args.weak_steps = args.e2e_frames = 0
+    return args
 
 
 def _free_port():
@@ -1437,6 +1456,34 @@ def _json_stdout():
     return os.fdopen(fd, "w", buffering=1)
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, vbg, owned=None):
+    """--dump-outputs: what the timed path's last step computed, as a caller gets it from
+    VoxelBlockGrid.export() (with N > 1 ranks: rank 0's owned slice of the merged shard) --
+    keys.npy (n, 3) float64 (the int32 block keys), tsdf.npy and weight.npy (n, R, R, R) float32,
+    blocks.npy [number of blocks in the volume] float64.  Blocks are written in ascending key order
+    (the buffer order follows the hash inserts' timing).  A volume over the 64 MB budget is
+    represented by a fixed sample of its blocks: positions in the key order drawn once with seed 0."""
+    import numpy as np
+    keys, tsdf, wgt = vbg.export()
+    if owned is not None:
+        keys, tsdf, wgt = keys[:owned], tsdf[:owned], wgt[:owned]
+    n = len(keys)
+    order = np.lexsort(keys.T[::-1])
+    per_block = 8 * vbg.block_resolution ** 3 + 24
+    fit = (DUMP_MAX_BYTES - 4096) // per_block  # (4 .npy headers and blocks.npy)
+    if n > fit:
+        order = order[np.sort(np.random.default_rng(0).choice(n, fit, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "keys.npy"), keys[order].astype(np.float64))
+    np.save(os.path.join(path, "tsdf.npy"), tsdf[order])
+    np.save(os.path.join(path, "weight.npy"), wgt[order])
+    np.save(os.path.join(path, "blocks.npy"), np.array([n], np.float64))
+    return {"dir": path, "blocks": n, "blocks_written": int(len(order))}
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ:
@@ -1588,6 +1635,12 @@ def main():
     log(f"rank {rank}: {args.steps} timed steps in {elapsed:.3f} s")
     vbg.profile(False)
     st = vbg.stats(reset=True)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # before any other leg touches the volume
+        dumped = (dump_outputs(args.dump_outputs, shard["out"], shard["owned"]) if world > 1
+                  else dump_outputs(args.dump_outputs, vbg))
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     # the touch launches' times (HIP events on the touch stream) from a separate profiled pass of the
     # same step: recorded inside the timed steps they would add two event commands per batch
     tst = None
@@ -1626,7 +1679,7 @@ def main():
     R3_ = args.block_resolution ** 3
     ext_ms, (nv, nt) = (None, (0, 0))
     sharded = sharded_par = weak_leg = c5_sharded = None
-    if world > 1:
+    if world > 1 and args.full:
         # every rank extracts its owned cubes (mqr_extract_mesh_owned); the mesh is the concatenation
         from mqr.distributed import extract_mesh_owned
         dist.barrier()
@@ -1710,7 +1763,7 @@ def main():
                 log(f"rank {rank}: C5 sharded sub-leg failed: {type(e).__name__}: {e}")
                 c5_sharded = {"error": f"rank {rank}: {type(e).__name__}: {e}"}
             torch.cuda.empty_cache()
-    elif rank == 0:
+    elif rank == 0 and world == 1 and args.extract_reps > 0:
         ext_ms, (nv, nt) = extract_ms(vbg, args.extract_threshold, args.extract_reps)
 
     R3 = args.block_resolution ** 3
@@ -1797,6 +1850,8 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3,
+            "full": args.full,
+            "outputs": dumped,
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
@@ -1821,12 +1876,12 @@ def main():
             "merge_transport": transport,
             "merge_bytes_per_rank": merge_bytes,
             "weak_c2": weak_leg,
-            "union_blocks": blocks if world > 1 else None,
+            "union_blocks": blocks if sharded else None,
             "extract_ms": ext_ms,
             "extract": {"weight_threshold": args.extract_threshold, "vertices": nv, "triangles": nt,
                         "blocks": blocks, "alg_gbs": ext_alg,
                         "note": "device-resident extract_triangle_mesh, median of reps; alg bytes = "
-                                "8R^3 N + 108 N + 24 V + 12 T"},
+                                "8R^3 N + 108 N + 24 V + 12 T"} if (ext_ms or sharded) else None,
             "confidence": extras.get("confidence"),
             "ingest": extras.get("ingest"),
             "raycast": extras.get("raycast"),
@@ -1847,9 +1902,9 @@ def main():
                          "touch_ms_per_launch": (tst["touch_ms"] / tst["touch_launches"]) if tst and
                          tst["touch_launches"] else None,
                          "touch_launches_per_step": (tst["touch_launches"] / args.touch_steps) if tst else None,
-                         "touch_note": f"k_touch launch time (HIP events on the touch stream) over {args.touch_steps} "
-                                       "profiled steps after the timed ones; the first touch of a step runs alone, the "
-                                       "others beside the previous batch's integrate"},
+                         "touch_note": (f"k_touch launch time (HIP events on the touch stream) over {args.touch_steps} "
+                                        "profiled steps after the timed ones; the first touch of a step runs alone, the "
+                                        "others beside the previous batch's integrate") if tst else None},
             "cpu_baseline": cpu,
             "parity": parity,
             "c3": extras.get("c3"),

@@ -16,3 +16,17 @@ def pytest_configure(config):
 @pytest.fixture(scope="session")
 def golden_dir():
     return os.path.join(ROOT, "tests", "golden")
+
+
+@pytest.fixture(scope="session")
+def confidence_golden(golden_dir):
+    """The confidence golden vectors as one read-only mapping (<seq>_<field> -> array).  They are
+    stored one file per sequence, confidence_golden_<seq>.npz, so that each stays under 1 MiB."""
+    import numpy as np
+    out = {}
+    for seq in ("sphere", "room"):
+        with np.load(os.path.join(golden_dir, f"confidence_golden_{seq}.npz")) as z:
+            for k in z.files:
+                out[k] = z[k]
+                out[k].setflags(write=False)
+    return out

@@ -9,7 +9,7 @@ copied; the GPU box never sees the reference -- only these vectors.
 Fixtures:
   decode_golden.npz      raw NDC buffers x (near, far) -> convert_depth_to_linear (depth_utils.py:21-46)
                          + is_depth_map_valid verdicts (depth_data_io.py:80-85)
-  confidence_golden.npz  per sequence (sphere / room): the capture (raw buffers + descriptor rows), the
+  confidence_golden_<seq>.npz  per sequence (sphere / room): the capture (raw buffers + descriptor rows), the
                          DepthDataset fields and compute_o3d_intrinsic_matrices (o3d_utils.py:14-19,
                          <seq>_fx / _cx / _K), the OPEN3D extrinsics_wc / _cw (transforms.py:57-72,
                          164-220) and np.linalg.inv(extrinsics_cw), the decoded depth; then
@@ -126,7 +126,9 @@ def make_dataset_and_confidence(ref):
             out[f"{name}_err"] = np.stack([
                 ref["compute_pixel_error_map"](K, T_cw, T_cw_inv, a, depths[a], b, depths[b], depth_max=3.0)
                 for a, b in pairs])
-    np.savez_compressed(HERE / "confidence_golden.npz", **out)
+    for seq in ("sphere", "room"):  # one file per sequence: each stays under 1 MiB
+        np.savez_compressed(HERE / f"confidence_golden_{seq}.npz",
+                            **{k: v for k, v in out.items() if k.startswith(seq + "_")})
 
 
 def make_ragged_confidence(ref):

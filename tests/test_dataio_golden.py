@@ -17,8 +17,8 @@ def decode(golden_dir):
 
 
 @pytest.fixture(scope="module")
-def golden(golden_dir):
-    return np.load(os.path.join(golden_dir, "confidence_golden.npz"))
+def golden(confidence_golden):
+    return confidence_golden
 
 
 def test_decode_matches_reference(decode):

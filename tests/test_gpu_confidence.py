@@ -8,11 +8,10 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
-def golden(golden_dir):
-    import os
+def golden(confidence_golden):
     from mqr import _lib
     _lib.load()
-    return np.load(os.path.join(golden_dir, "confidence_golden.npz"))
+    return confidence_golden
 
 
 @pytest.mark.parametrize("name", ["sphere", "room"])

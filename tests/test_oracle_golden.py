@@ -8,8 +8,8 @@ import oracle
 
 
 @pytest.fixture(scope="module")
-def golden(golden_dir):
-    return np.load(os.path.join(golden_dir, "confidence_golden.npz"))
+def golden(confidence_golden):
+    return confidence_golden
 
 
 @pytest.mark.parametrize("name", ["sphere", "room"])

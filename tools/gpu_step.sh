@@ -5,11 +5,11 @@
 #   tests       the whole `pytest -m gpu` suite                      -> gpurun_out/${TAG}_gpu_tests.log
 #   tests:F     pytest -m gpu on the test files F (comma separated)   -> gpurun_out/${TAG}_gpu_tests.log
 #   smoke       __graft_entry__.smoke()                               -> gpurun_out/${TAG}_smoke.log
-#   bench       the default bench line (N = 1)                        -> gpurun_out/${TAG}_bench.json
-#   benchq      a short bench (no C4 / C5 / drop-in legs)             -> gpurun_out/${TAG}_benchq.json
+#   bench       the whole bench line (N = 1, bench.py --full)         -> $OUT/${TAG}_bench.json
+#   benchq      a short --full bench (no C4 / C5 / drop-in legs)      -> $OUT/${TAG}_benchq.json
 #   c5          the C5 leg alone, parity included (bench.py --c5-only)   -> gpurun_out/${TAG}_c5.json
-#   n2          2-rank rehearsal on one GPU (gloo-staged merge)        -> gpurun_out/${TAG}_bench_n2.json
-#   n2self      the same, bench.py --gpus 2 starting its own ranks (no torchrun) -> gpurun_out/${TAG}_bench_n2_selflaunch.json
+#   n2          2-rank --full rehearsal on one GPU (gloo-staged merge)  -> $OUT/${TAG}_bench_n2.json
+#   n2self      the same, bench.py --gpus 2 starting its own ranks (no torchrun) -> $OUT/${TAG}_bench_n2_selflaunch.json
 #   mbytes      C4 exchange bytes / zero-weight voxels / per-rank times at 2, 4, 8 ranks (tools/merge_bytes.py)
 #   steptrace   kernel trace of the C2 loop: step head (tools/step_head.py) and integrate-stream gaps (tools/integrate_gaps.py)
 #   prof        rocprofv3 --kernel-trace --stats of the C2 bench      -> gpurun_out/${TAG}_bench_kernel_stats.csv
@@ -29,6 +29,8 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
+OUT=${OUT:-build/steps}  # where the bench steps write (build/ is not tracked)
+mkdir -p "$OUT"
 export TMPDIR=/tmp
 TAG=${TAG:-r06}
 PYT="python -u -m pytest -x -v --timeout 300 --timeout-method thread -m gpu"
@@ -46,23 +48,23 @@ for step in ${STEPS:-tests}; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${TAG}_smoke.log 2>&1 || { tail -20 gpurun_out/${TAG}_smoke.log; exit 1; }
       tail -1 gpurun_out/${TAG}_smoke.log ;;
     bench)
-      timeout -k 10 900 python bench.py > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || { tail -30 gpurun_out/${TAG}_bench.err; exit 1; }
-      tail -c 400 gpurun_out/${TAG}_bench.json ;;
+      timeout -k 10 900 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err || { tail -30 $OUT/${TAG}_bench.err; exit 1; }
+      tail -c 400 $OUT/${TAG}_bench.json ;;
     benchq)
-      timeout -k 10 600 python bench.py --no-c4 --no-c5 --e2e-frames 0 > gpurun_out/${TAG}_benchq.json 2> gpurun_out/${TAG}_benchq.err || { tail -30 gpurun_out/${TAG}_benchq.err; exit 1; }
-      tail -c 400 gpurun_out/${TAG}_benchq.json ;;
+      timeout -k 10 600 python bench.py --full --no-c4 --no-c5 --e2e-frames 0 > $OUT/${TAG}_benchq.json 2> $OUT/${TAG}_benchq.err || { tail -30 $OUT/${TAG}_benchq.err; exit 1; }
+      tail -c 400 $OUT/${TAG}_benchq.json ;;
     c5)
       timeout -k 10 900 python bench.py --c5-only > gpurun_out/${TAG}_c5.json 2> gpurun_out/${TAG}_c5.err || { tail -30 gpurun_out/${TAG}_c5.err; exit 1; }
       tail -c 1500 gpurun_out/${TAG}_c5.json ;;
     n2)
       MQR_BENCH_WRAP_DEVICES=1 timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 2 --weak-steps 10 \
-        > gpurun_out/${TAG}_bench_n2.json 2> gpurun_out/${TAG}_bench_n2.err || { tail -40 gpurun_out/${TAG}_bench_n2.err; exit 1; }
-      tail -c 600 gpurun_out/${TAG}_bench_n2.json ;;
+        --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --full --steps 10 --warmup 2 --weak-steps 10 \
+        > $OUT/${TAG}_bench_n2.json 2> $OUT/${TAG}_bench_n2.err || { tail -40 $OUT/${TAG}_bench_n2.err; exit 1; }
+      tail -c 600 $OUT/${TAG}_bench_n2.json ;;
     n2self)
-      MQR_BENCH_WRAP_DEVICES=1 timeout -k 10 900 python bench.py --gpus 2 --steps 10 --warmup 2 --weak-steps 10 \
-        > gpurun_out/${TAG}_bench_n2_selflaunch.json 2> gpurun_out/${TAG}_bench_n2_selflaunch.err || { tail -40 gpurun_out/${TAG}_bench_n2_selflaunch.err; exit 1; }
-      tail -c 600 gpurun_out/${TAG}_bench_n2_selflaunch.json ;;
+      MQR_BENCH_WRAP_DEVICES=1 timeout -k 10 900 python bench.py --gpus 2 --full --steps 10 --warmup 2 --weak-steps 10 \
+        > $OUT/${TAG}_bench_n2_selflaunch.json 2> $OUT/${TAG}_bench_n2_selflaunch.err || { tail -40 $OUT/${TAG}_bench_n2_selflaunch.err; exit 1; }
+      tail -c 600 $OUT/${TAG}_bench_n2_selflaunch.json ;;
     mbytes)
       timeout -k 10 600 python tools/merge_bytes.py > gpurun_out/${TAG}_merge_bytes.json 2> gpurun_out/${TAG}_merge_bytes.err || { tail -30 gpurun_out/${TAG}_merge_bytes.err; exit 1; }
       tail -8 gpurun_out/${TAG}_merge_bytes.err ;;

@@ -413,6 +413,41 @@ int mqr_mesh_filter_components(int device, const float* vertices, const float* n
                                const int32_t* triangles, int64_t nt, int loc, int64_t min_triangle_count,
                                mqr_geom** out, int64_t* stats);
 
+/* Fragment registration (refine_fragment_poses.py:122-271): a CLOUD SET of N float32 xyz clouds in
+ * HBM and three batched operations over pairs of them, standing in for Open3D's
+ * evaluate_registration, multi_scale_icp (point to point) and get_information_matrix.
+ * create: points[i] -> counts[i] x 3 float32, all in `loc` memory.  MQR_HOST clouds are copied;
+ * MQR_DEVICE clouds are used IN PLACE (no copy): the caller keeps them allocated and unchanged until
+ * mqr_cloudset_destroy.  Fails on an empty cloud or a non-finite coordinate.  The set caches, per
+ * cloud, each point selection asked for (full, every k-th point, voxel down-sample at v) and a
+ * uniform-grid index per (selection, search radius); a coordinate whose cell index would pass 2^20
+ * per axis fails the call that needs the view.
+ * voxel_down: the down-sampled view of one cloud (key floor(p / v) per axis in float64, members
+ * summed in ascending original index in float64, output in ascending (kx, ky, kz) order); *n
+ * receives the point count, `out` (may be NULL to ask for the count only) n x 3 float32 in `loc`.
+ * Pairs: src[p], tgt[p] index the set's clouds; T row-major 4x4 float64 per pair (source to target).
+ * evaluate_pairs: fitness = correspondences / source points and inlier rmse of T, on every k-th
+ * point of both clouds (every_k <= 1: all points).
+ * icp_pairs: per level l both clouds voxel down-sampled at voxel_sizes[l] (<= 0: the full cloud),
+ * up to max_iters[l] point-to-point iterations at max_dists[l] with Open3D's relative fitness / rmse
+ * stopping rule; T_out, fitness, rmse of the last level; iterations[p * n_levels + l] = the
+ * correspondence passes pair p ran on level l.
+ * information_pairs: Open3D's 6x6 information matrix of T over the FULL clouds, info[36] per pair.
+ * Results are deterministic: a repeated call, alone or in any batch, is bit-identical. */
+typedef struct mqr_cloudset mqr_cloudset;
+int mqr_cloudset_create(int device, int n_clouds, const float* const* points, const int64_t* counts, int loc,
+                        mqr_cloudset** out);
+int mqr_cloudset_destroy(mqr_cloudset* set);
+int mqr_cloudset_voxel_down(mqr_cloudset* set, int cloud, double voxel_size, int64_t* n, float* out, int loc);
+int mqr_evaluate_pairs(mqr_cloudset* set, int n_pairs, const int32_t* src, const int32_t* tgt, int every_k,
+                       double max_dist, const double* T, double* fitness, double* rmse, int64_t* ncorr);
+int mqr_icp_pairs(mqr_cloudset* set, int n_pairs, const int32_t* src, const int32_t* tgt, int n_levels,
+                  const double* voxel_sizes, const double* max_dists, const int32_t* max_iters,
+                  const double* rel_fitness, const double* rel_rmse, const double* T_init, double* T_out,
+                  double* fitness, double* rmse, int32_t* iterations);
+int mqr_information_pairs(mqr_cloudset* set, int n_pairs, const int32_t* src, const int32_t* tgt, double max_dist,
+                          const double* T, double* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,15 @@ SIGNATURES = {
     "mqr_check_division": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint64,
                                           ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     "mqr_vbg_stats": (ctypes.c_int, [_vp, ctypes.POINTER(MqrStats), ctypes.c_int]),
+    "mqr_cloudset_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp), _i64p, ctypes.c_int,
+                                           ctypes.POINTER(_vp)]),
+    "mqr_cloudset_destroy": (ctypes.c_int, [_vp]),
+    "mqr_cloudset_voxel_down": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_double, _i64p, _vp, ctypes.c_int]),
+    "mqr_evaluate_pairs": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_int, ctypes.c_double, _f64p,
+                                          _f64p, _f64p, _i64p]),
+    "mqr_icp_pairs": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_int, _f64p, _f64p, _i32p, _f64p,
+                                     _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
+    "mqr_information_pairs": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_double, _f64p, _f64p]),
 }
 
 _lib = None
@@ -238,6 +247,7 @@ ORDERED = frozenset({
     "mqr_color_vertices",
     "mqr_color_map", "mqr_scene_add_triangles", "mqr_scene_cast_pinhole", "mqr_scene_cast_rays",
     "mqr_mesh_filter_components", "mqr_memcpy",
+    "mqr_cloudset_create", "mqr_cloudset_voxel_down", "mqr_evaluate_pairs", "mqr_icp_pairs", "mqr_information_pairs",
 })
 _tls = threading.local()
 

@@ -4,6 +4,9 @@
         scripts/processing/reconstruction/depth_optimization/refine_fragment_poses.py:14-58
     integrate_fragment_point_clouds(depth_data_io, fragment_dataset_map, config, workers)
         the parallel part of integrate_and_save_fragment_point_clouds (:61-119), without the saving
+    compute_pcd_pair_edge(clouds, source_node, target_node, config, uncertain)            :122-193
+    build_pose_graph_for_scene(fragment_clouds_by_side, config)                           :196-271
+        the pose-graph edges of every fragment pair, registered on the GPU (mqr.registration)
 
 Each fragment (``fragment_size`` = 100 frames, pipeline_config.yml:38) is integrated into a FRESH
 volume (``vbg_opt=None``) and its point cloud extracted with the default weight threshold 3.0; a
@@ -15,10 +18,11 @@ MI355X.  Worker results cross the process boundary as (side, positions, normals)
 """
 from __future__ import annotations
 
+import itertools
 import multiprocessing
 import os
-from dataclasses import dataclass
-from typing import Optional
+from dataclasses import dataclass, field
+from typing import List, Optional
 
 import numpy as np
 
@@ -27,8 +31,8 @@ from .models import Side
 
 @dataclass
 class FragmentPoseRefinementConfig:
-    """The integration fields of reconstruction_config.py:60-84 (defaults; the pipeline's values are
-    in config/pipeline_config.yml:50-58)."""
+    """reconstruction_config.py:60-84 (defaults; the pipeline's values are in
+    config/pipeline_config.yml:50-58): the integration fields, then the registration fields."""
     device: object = "CUDA:0"
     use_confidence_filtered_depth: bool = True
     confidence_threshold: float = 0.05
@@ -39,6 +43,26 @@ class FragmentPoseRefinementConfig:
     depth_max: float = 1.5
     trunc_voxel_multiplier: float = 8.0
     use_multi_threading: bool = False
+    use_pre_filtering: bool = True
+    pre_filter_every_k_points: float = 30
+    pre_filter_max_corr_dist: float = 0.1
+    pre_filter_inlier_rmse_threshold: float = 0.05
+    pre_filter_fitness_threshold: float = 0.2
+    icp_voxel_sizes: List[float] = field(default_factory=lambda: [0.05, 0.025, 0.0125])
+    max_corr_dists: List[float] = field(default_factory=lambda: [0.1, 0.05, 0.025])
+    max_iterations: List[int] = field(default_factory=lambda: [50, 31, 14])
+    relative_fitnesses: List[float] = field(default_factory=lambda: [1e-6, 1e-6, 1e-6])
+    relative_rmses: List[float] = field(default_factory=lambda: [1e-6, 1e-6, 1e-6])
+    icp_fitness_threshold: float = 0.2
+    icp_inlier_rmse_threshold: float = 0.05
+    dist_threshold: float = 0.07
+    edge_prune_threshold: float = 0.25
+
+    @property
+    def icp_criteria_list(self):
+        from .registration import ICPConvergenceCriteria
+        return [ICPConvergenceCriteria(relative_fitness=f, relative_rmse=r, max_iteration=i)
+                for f, r, i in zip(self.relative_fitnesses, self.relative_rmses, self.max_iterations)]
 
 
 def integrate_fragment_point_cloud(depth_data_io, frag_dataset, side: Side, config: FragmentPoseRefinementConfig):
@@ -96,13 +120,19 @@ def _warm(_):
 
 
 def integrate_fragment_point_clouds(depth_data_io, fragment_dataset_map, config: FragmentPoseRefinementConfig,
-                                    workers: Optional[int] = None, pool=None):
+                                    workers: Optional[int] = None, pool=None, keep_on_device: bool = False):
     """Every fragment of every side through integrate_fragment_point_cloud, in the reference's
     argument order (sides, then fragments).  With config.use_multi_threading: a spawn Pool of
     `workers` processes (default cpu_count - 1, at most 15: one GPU holds a bounded number of
-    contexts), or the caller's `pool`.  Returns [(side, positions, normals) | None] in argument order."""
+    contexts), or the caller's `pool`.  Returns [(side, positions, normals) | None] in argument order.
+    With keep_on_device (in-process only) the entries are (side, PointCloud) with the cloud left in
+    HBM, ready for build_pose_graph_for_scene without a trip over PCIe."""
     args = [(i, depth_data_io, ds, side, config)
             for i, (side, ds) in enumerate((s, d) for s, dss in fragment_dataset_map.items() for d in dss)]
+    if keep_on_device:
+        if config.use_multi_threading or pool is not None:
+            raise ValueError("keep_on_device needs the in-process path: device memory does not cross processes")
+        return [integrate_fragment_point_cloud(io, ds, side, cfg) for _, io, ds, side, cfg in args]
     if not config.use_multi_threading:
         out = [_worker(a) for a in args]
     elif pool is not None:
@@ -123,3 +153,145 @@ def fragment_datasets(dataset, fragment_size: int = 100):
     its odometry and loop closure are out of scope)."""
     n = len(dataset)
     return [dataset[list(range(a, min(n, a + fragment_size)))] for a in range(0, n, fragment_size)]
+
+
+# ---- pose graph of the fragments (refine_fragment_poses.py:122-271) --------------------------------
+# Plain containers with Open3D's attribute names; to_legacy() gives the real
+# o3d.pipelines.registration objects when open3d imports (as mqr.geometry does).  The optimisation of
+# the graph (o3d.pipelines.registration.global_optimization) is not part of this package.
+@dataclass
+class PoseGraphNode:
+    pose: np.ndarray = field(default_factory=lambda: np.eye(4))
+
+    def to_legacy(self):
+        from .geometry import _try_open3d
+        o3d = _try_open3d()
+        return self if o3d is None else o3d.pipelines.registration.PoseGraphNode(pose=np.asarray(self.pose))
+
+
+@dataclass
+class PoseGraphEdge:
+    source_node_id: int = -1
+    target_node_id: int = -1
+    transformation: np.ndarray = field(default_factory=lambda: np.eye(4))
+    information: np.ndarray = field(default_factory=lambda: np.eye(6))
+    uncertain: bool = False
+    confidence: float = 1.0
+
+    def to_legacy(self):
+        from .geometry import _try_open3d
+        o3d = _try_open3d()
+        if o3d is None:
+            return self
+        return o3d.pipelines.registration.PoseGraphEdge(
+            source_node_id=self.source_node_id, target_node_id=self.target_node_id,
+            transformation=np.asarray(self.transformation), information=np.asarray(self.information),
+            uncertain=self.uncertain, confidence=self.confidence)
+
+
+@dataclass
+class PoseGraph:
+    nodes: List[PoseGraphNode] = field(default_factory=list)
+    edges: List[PoseGraphEdge] = field(default_factory=list)
+
+    def to_legacy(self):
+        from .geometry import _try_open3d
+        o3d = _try_open3d()
+        if o3d is None:
+            return self
+        g = o3d.pipelines.registration.PoseGraph()
+        for n in self.nodes:
+            g.nodes.append(n.to_legacy())
+        for e in self.edges:
+            g.edges.append(e.to_legacy())
+        return g
+
+
+def _pre_filter_rejects(result, config) -> bool:
+    return (result.fitness < config.pre_filter_fitness_threshold
+            or result.inlier_rmse > config.pre_filter_inlier_rmse_threshold)
+
+
+def _icp_converged(result, config) -> bool:
+    # the reference's stand-in for Open3D's always-false `converged` flag (refine_fragment_poses.py:163-172)
+    return result.fitness >= config.icp_fitness_threshold or result.inlier_rmse <= config.icp_inlier_rmse_threshold
+
+
+def compute_pcd_pair_edge(clouds, source_node: int, target_node: int, config: FragmentPoseRefinementConfig,
+                          uncertain: bool) -> Optional[PoseGraphEdge]:
+    """refine_fragment_poses.py:122-193 for one pair, through the single-pair registration functions.
+    `clouds`: the fragment clouds by node index (PointClouds, device or host arrays)."""
+    from . import registration as reg
+    source, target = clouds[source_node], clouds[target_node]
+    if config.use_pre_filtering and uncertain:
+        cs = reg.CloudSet([source, target])
+        try:
+            pre = cs.evaluate_pairs([0], [1], config.pre_filter_max_corr_dist, np.eye(4),
+                                    every_k=int(config.pre_filter_every_k_points))[0]
+        finally:
+            cs.close()
+        if _pre_filter_rejects(pre, config):
+            return None
+    icp = reg.multi_scale_icp(source, target, config.icp_voxel_sizes, config.icp_criteria_list,
+                              config.max_corr_dists, np.eye(4))
+    if uncertain and not _icp_converged(icp, config):
+        return None
+    info = reg.get_information_matrix(source, target, config.max_corr_dists[-1], icp.transformation)
+    return PoseGraphEdge(source_node, target_node, icp.transformation, info, uncertain, 1.0)
+
+
+def pose_graph_pairs(fragment_counts):
+    """(source node, target node, uncertain) in the reference's order (:226-254): the odometry pairs
+    side by side, then every combination of two nodes as a loop closure."""
+    pairs, base = [], 0
+    for count in fragment_counts:
+        pairs += [(base + i, base + i + 1, False) for i in range(count - 1)]
+        base += count
+    pairs += [(a, b, True) for a, b in itertools.combinations(range(base), 2)]
+    return pairs
+
+
+def build_pose_graph_for_scene(fragment_clouds_by_side, config: FragmentPoseRefinementConfig, batched: bool = True,
+                               stats: Optional[dict] = None):
+    """refine_fragment_poses.py:196-271 over fragment clouds in memory: {side: [cloud, ...]} ->
+    (PoseGraph, [(side, index), ...]).  The same nodes (sides, then index) and pairs (odometry, then
+    itertools.combinations) as the reference; batched, the pairs run as three calls on one CloudSet --
+    pre-filter every uncertain pair, ICP the survivors and the odometry pairs, information for the
+    edges kept.  ``batched=False`` runs compute_pcd_pair_edge pair by pair instead.  `stats` (a dict)
+    receives the pair counts of each stage."""
+    from . import registration as reg
+    node_side_index_list = [(side, i) for side, cs in fragment_clouds_by_side.items() for i in range(len(cs))]
+    clouds = [c for cs in fragment_clouds_by_side.values() for c in cs]
+    graph = PoseGraph(nodes=[PoseGraphNode() for _ in clouds])
+    pairs = pose_graph_pairs([len(cs) for cs in fragment_clouds_by_side.values()])
+    edges: List[Optional[PoseGraphEdge]] = [None] * len(pairs)
+    if not batched:
+        edges = [compute_pcd_pair_edge(clouds, a, b, config, unc) for a, b, unc in pairs]
+    elif pairs:
+        cs = reg.CloudSet(clouds)
+        try:
+            alive = list(range(len(pairs)))
+            if config.use_pre_filtering:
+                unc = [i for i in alive if pairs[i][2]]
+                pre = cs.evaluate_pairs([pairs[i][0] for i in unc], [pairs[i][1] for i in unc],
+                                        config.pre_filter_max_corr_dist, np.eye(4),
+                                        every_k=int(config.pre_filter_every_k_points))
+                dropped = {i for i, r in zip(unc, pre) if _pre_filter_rejects(r, config)}
+                alive = [i for i in alive if i not in dropped]
+            icp = cs.icp_pairs([pairs[i][0] for i in alive], [pairs[i][1] for i in alive], config.icp_voxel_sizes,
+                               config.icp_criteria_list, config.max_corr_dists, np.eye(4))
+            kept = [(i, r) for i, r in zip(alive, icp) if not pairs[i][2] or _icp_converged(r, config)]
+            info = cs.information_pairs([pairs[i][0] for i, _ in kept], [pairs[i][1] for i, _ in kept],
+                                        config.max_corr_dists[-1],
+                                        np.stack([r.transformation for _, r in kept]) if kept else None)
+            for (i, r), m in zip(kept, info):
+                a, b, u = pairs[i]
+                edges[i] = PoseGraphEdge(a, b, r.transformation, m, u, 1.0)
+            if stats is not None:
+                stats.update(pairs=len(pairs), icp_pairs=len(alive), information_pairs=len(kept))
+        finally:
+            cs.close()
+    valid_edges = [e for e in edges if e is not None]
+    print(f"[Info] Valid edges: {len(valid_edges)} / {len(edges)}")
+    graph.edges.extend(valid_edges)
+    return graph, node_side_index_list

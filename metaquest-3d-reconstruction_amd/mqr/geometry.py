@@ -288,6 +288,26 @@ class PointCloud:
     def write_ply(self, path):
         _write_ply(path, self.points, self.normals)
 
+    def uniform_down_sample(self, every_k_points: int):
+        """Points 0, k, 2k, ... (``o3d.t.geometry.PointCloud.uniform_down_sample``) as a host cloud."""
+        k = int(every_k_points)
+        if k < 1:
+            raise ValueError("every_k_points must be >= 1")
+        return PointCloud(self.points[::k].copy(), self.normals[::k].copy(), device=self.device)
+
+    def voxel_down_sample(self, voxel_size: float):
+        """Mean position per occupied voxel, in ascending voxel order, computed on the GPU
+        (mqr.registration.CloudSet; a cloud held in HBM is read in place).  Positions only: the
+        registration path reads nothing else, so the result's normals are zero."""
+        from .registration import CloudSet
+        d = device_ptr(self.point.positions)
+        cs = CloudSet([self], d[1] if d else 0)
+        try:
+            p = cs.voxel_down_sample(0, voxel_size)
+        finally:
+            cs.close()
+        return PointCloud(p, np.zeros_like(p), device=self.device)
+
 
 class TriangleMesh:
     def __init__(self, vertices, normals, triangles, device=None):

@@ -328,15 +328,14 @@ typedef struct mqr_stats {
  * every touch launch (two more on the touch stream); results in mqr_vbg_stats. */
 int mqr_vbg_profile(mqr_vbg* v, int enable);
 
-/* Test / tuning hooks.  mqr_vbg_set_variant: low byte = integrate kernel (0 default = lean kernel
- * where its preconditions hold, 1 generic, 2 exact R-specialised, 3 lean with the plate map, 5 depth
- * from LDS tiles; all bit-identical, see launch_integrate in csrc/vbg.hip); bit 8 serialises touch and integrate, bit 9 keeps touch
+/* Test / tuning hooks.  mqr_vbg_set_variant: low byte = integrate kernel (0 default = the fast kernels
+ * where their preconditions hold, 1 generic, 2 exact R-specialised, 4 lean with dword gathers; all bit-identical,
+ * see launch_integrate in csrc/vbg.hip; any other value is rejected); bit 8 serialises touch and integrate, bit 9 keeps touch
  * order instead of longest-first, bit 10 uses 32-frame batches instead of 127 (bit 20: 64-frame
  * batches; bits 21 / 22 / 23: a first batch of 64 / 32 / 16 frames), bit 11 records
  * system-scope ordering events, bit 12 probes one table slot per new key in the batch touch (forces
- * the full-table undo-and-retry path; test hook), bit 13 sizes the table for the worst case, bit 14 makes
- * every integrate launch wait on a touch-stream event, bit 15 runs the batch in spatial per-XCD groups
- * (k_xcd_order; A/Bs), bit 16 gives the touch one stride-4 pixel per thread instead of two, bit 18 turns
+ * the full-table undo-and-retry path; test hook), bits 13-15 are retired and rejected (a rejected
+ * value returns non-zero, sets mqr_last_error and leaves the volume's configuration as it was), bit 16 gives the touch one stride-4 pixel per thread instead of two, bit 18 turns
  * off the speculative first-batch integrate (k_gate; A/B), bit 24 makes mqr_integrate_frames on device frames
  * drain its streams before returning (A/B), bit 25 makes mqr_vbg_reset wait for an integrate in flight
  * instead of swapping in the second table / pool set (A/B), bit 26 runs the default integrate without its LDS

@@ -36,6 +36,10 @@
 #include "mqr_common.hpp"
 #include "mqr_mc_tables.h"
 
+#ifndef MQR_AB
+#define MQR_AB 0  // 1: the extraction A/B modes (tools/_ab/libmqr_ab.so only, tools/ab_extract.py)
+#endif
+
 namespace mqr {
 
 constexpr int kMaxR = 16;

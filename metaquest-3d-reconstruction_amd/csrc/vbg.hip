@@ -23,9 +23,6 @@
 
 #include "mqr_common.hpp"
 #include "vbg_kernels.hpp"
-#if MQR_AB
-#include "vbg_ab.hpp"
-#endif
 
 namespace mqr {
 
@@ -155,8 +152,7 @@ static int ensure_lists(mqr_vbg* v, int64_t cap) {
         if (v->lpt[p]) MQR_CHECK_HIP(hipFree(v->lpt[p]));
         v->lists[p] = v->lpt[p] = nullptr;
         MQR_CHECK_HIP(hipMalloc(&v->lists[p], sizeof(int32_t) * cap));
-        // slots, then their masks, then k_xcd_order's group byte per entry
-        MQR_CHECK_HIP(hipMalloc(&v->lpt[p], (sizeof(int32_t) + sizeof(bmask_t) + 1) * cap));
+        MQR_CHECK_HIP(hipMalloc(&v->lpt[p], (sizeof(int32_t) + sizeof(bmask_t)) * cap));  // slots, then masks
         if (v->bad[p]) MQR_CHECK_HIP(hipFree(v->bad[p]));
         v->bad[p] = nullptr;
         MQR_CHECK_HIP(hipMalloc(&v->bad[p], (sizeof(int32_t) + sizeof(bmask_t)) * cap));  // slots, then masks
@@ -238,7 +234,7 @@ static int ensure_depth(mqr_vbg* v, int64_t floats) {
     return 0;
 }
 
-// Whether one Markstein correction gives IEEE s / t for every s in [-t, t] (k_integrate_wt<.., 1>, lean_update_v<DIV1>):
+// Whether one Markstein correction gives IEEE s / t for every s in [-t, t] (k_integrate_wt<.., 1>):
 // k_check_strunc over the ~1e9 floats of [+0, t] once per t per process (a few ms; the sequence is
 // odd in s).  Cached; on any error the answer is false (two corrections stay).
 static bool strunc_one_correction_ok(float t) {
@@ -270,161 +266,6 @@ static bool strunc_one_correction_ok(float t) {
     cache[tb] = ok;
     return ok;
 }
-
-#if MQR_AB
-// The A/B library's integrate variants (launch_integrate's variant list; kernels in vbg_ab.hpp).  *fixup: the
-// caller runs the exact fix-up launch behind the kernel (the kernels that hand blocks back).
-static int launch_integrate_ab(mqr_vbg* v, int var, hipStream_t s, unsigned grid, unsigned lean_grid, int grouped,
-                               const int32_t* list, const bmask_t* lmask, int* counters, const Table& t,
-                               const float* depths, int64_t HW, int H, int W, const FrameParams* fp,
-                               const int64_t* depth_frame, float depth_max, float sdf_trunc, int first_new,
-                               int32_t* bad_out, bool* fixup, int nframes) {
-    // k_integrate_lean_ab<16, 512, MAP, WPE, ILP, PAIR, DIV1, ZBLK, FIXIN>
-    auto lean = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(lean_grid), dim3(512), 0, s, list, lmask, bad_out, counters, v->list_cap, t,
-                           v->pool, v->voxel_size, depths, HW, H, W, fp, depth_frame, depth_max, sdf_trunc, first_new,
-                           grouped);
-    };
-    auto win = [&](auto kern, unsigned nt) {
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(nt), 0, s, list, lmask, counters, v->list_cap, t, v->pool,
-                           v->voxel_size, depths, HW, H, W, fp, depth_frame, depth_max, sdf_trunc, first_new);
-    };
-    auto wx = [&](auto kern) {  // k_integrate_wx: the window kernel's arguments plus the fix-up list
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, s, list, lmask, bad_out, counters, v->list_cap, t, v->pool,
-                           v->voxel_size, depths, HW, H, W, fp, depth_frame, depth_max, sdf_trunc, first_new);
-    };
-    *fixup = var <= 22;
-    switch (var) {
-        case 3: lean(k_integrate_lean_ab<16, 512>); break;  // plate map
-        case 5:
-            hipLaunchKernelGGL((k_integrate_lt<1>), dim3(grid), dim3(512), 0, s, list, lmask, bad_out, counters, v->list_cap, t, v->pool, v->voxel_size, depths, HW, H, W, fp, depth_frame,
-                               depth_max, sdf_trunc, first_new);
-            break;
-        case 6: lean(k_integrate_lean_ab<16, 512, 1, 8, 1, 1>); break;  // paired gathers, 8 waves (spills)
-        case 7: lean(k_integrate_lean_ab<16, 512, 1, 6, 1, 1>); break;  // paired gathers, 6 waves
-        case 8: lean(k_integrate_lean_ab<16, 512, 1, 8, 2, 2>); break;  // VALU-lean projection / update
-        case 9: lean(k_integrate_lean_ab<16, 512, 1, 8, 2, 3>); break;  // + zc checked per block
-        case 10:                                                         // + one-correction s / trunc
-            if (strunc_one_correction_ok(sdf_trunc)) lean(k_integrate_lean_ab<16, 512, 1, 8, 2, 3, 1>);
-            else lean(k_integrate_lean_ab<16, 512, 1, 8, 2, 3>);
-            break;
-        case 11: lean(k_integrate_lean_ab<16, 512, 1, 5, 2, 4>); break;  // 16-byte windows, >= 5 waves
-        case 12: lean(k_integrate_lean_ab<16, 512, 1, 4, 2, 4>); break;  // 16-byte windows, >= 4 waves
-        case 13: lean(k_integrate_lean_ab<16, 512, 1, 6, 2, 5>); break;  // 8-byte windows, >= 6 waves
-        case 14: lean(k_integrate_lean_ab<16, 512, 1, 5, 1, 4>); break;  // 16-byte windows, ILP 1
-        case 15: lean(k_integrate_lean_ab<16, 512, 1, 7, 2, 5>); break;  // the round-3 default (fix-up launch)
-        case 16: lean(k_integrate_lean_ab<16, 512, 1, 6, 2, 5, 0, true>); break;  // zc checked per block
-        case 17:                                                                  // 16 + one-correction
-            if (strunc_one_correction_ok(sdf_trunc)) lean(k_integrate_lean_ab<16, 512, 1, 6, 2, 5, 1, true>);
-            else lean(k_integrate_lean_ab<16, 512, 1, 6, 2, 5, 0, true>);
-            break;
-        case 18: lean(k_integrate_lean_ab<16, 512, 1, 6, 4, 5>); break;  // 4 interleaved voxel chains
-        case 19: lean(k_integrate_lean_ab<16, 512, 1, 6, 2, 6>); break;  // 16-byte windows in two halves
-        case 20: lean(k_integrate_lean_ab<16, 512, 1, 7, 2, 7>); break;  // 8-byte windows in two halves
-        case 21:                                                          // default + one-correction
-            if (strunc_one_correction_ok(sdf_trunc)) lean(k_integrate_lean_ab<16, 512, 1, 6, 2, 5, 1>);
-            else lean(k_integrate_lean_ab<16, 512, 1, 7, 2, 5>);
-            break;
-        case 22:  // 21 + zc checked per block, >= 5 waves
-            if (strunc_one_correction_ok(sdf_trunc)) lean(k_integrate_lean_ab<16, 512, 1, 5, 2, 5, 1, true>);
-            else lean(k_integrate_lean_ab<16, 512, 1, 7, 2, 5>);
-            break;
-        case 23: lean(k_integrate_lean_ab<16, 512, 1, 7, 2, 5, 0, false, true>); break;  // the round-4 default
-        case 24: win(k_integrate_win_ab<512, 7, 0>, 512); break;    // plain frame loop
-        case 25: win(k_integrate_win_ab<512, 6, 1>, 512); break;    // frames pipelined, >= 6 waves
-        case 26: win(k_integrate_win_ab<1024, 8, 1>, 1024); break;  // 1024 threads, frames pipelined
-        case 27: win(k_integrate_win_ab<1024, 8, 0>, 1024); break;  // 1024 threads, plain
-        case 28: win(k_integrate_win_ab<512, 7, 1>, 512); break;    // frames pipelined, >= 7 waves
-        case 29: win(k_integrate_win_ab<512, 7, 2>, 512); break;    // half-frame pipeline, >= 7 waves
-        case 30: win(k_integrate_win_ab<1024, 8, 2>, 1024); break;  // half-frame pipeline, 1024 threads
-        case 31: win(k_integrate_win_ab<512, 6, 2>, 512); break;    // half-frame pipeline, >= 6 waves
-        case 32: win(k_integrate_win_ab<512, 7, 0, 1>, 512); break;  // timing diagnostics (wrong results)
-        case 33: win(k_integrate_win_ab<512, 7, 0, 2>, 512); break;
-        case 34: win(k_integrate_win_ab<512, 6, 2, 1>, 512); break;
-        case 35: win(k_integrate_win_ab<512, 6, 2, 2>, 512); break;
-        case 36: win(k_integrate_pk<7, 0>, 512); break;  // packed FP32
-        case 37: win(k_integrate_pk<7, 2>, 512); break;
-        case 38: win(k_integrate_pk<6, 2>, 512); break;
-        case 39: win(k_integrate_pk<6, 0>, 512); break;
-        // branch-free forms: 40 window offsets selected, 41 updates selected, 42 both, 43 both at >= 6 waves
-        case 40: win(k_integrate_win_ab<512, 7, 0, 0, 1>, 512); break;
-        case 41: win(k_integrate_win_ab<512, 7, 0, 0, 2>, 512); break;
-        case 42: win(k_integrate_win_ab<512, 7, 0, 0, 3>, 512); break;
-        case 43: win(k_integrate_win_ab<512, 6, 0, 0, 3>, 512); break;
-        case 44: win(k_integrate_win_r4<7>, 512); break;  // the round-4 default's source
-        case 45:    // lane-level tile proofs (k_tile_records + k_integrate_tp), >= 7 waves
-        case 46:    // the same at >= 6 waves
-        case 47:    // record loads of all 8 voxels first, >= 7 waves
-        case 48:    // the same at >= 5 waves
-        case 49:    // 45 branch-free: every lane issues the window read, decided lanes past the end
-        case 50: {  // 47 branch-free
-            // per device, grow-only (A/B library only): the batch's 8 x 4 tile records, 8 B each
-            static void* rec_buf[64] = {};
-            static size_t rec_cap[64] = {};
-            const int TW = (W + 7) / 8, TH = (H + 3) / 4;
-            const size_t need = sizeof(uint2) * (size_t)TW * TH * (size_t)std::max(nframes, 1);
-            MQR_REQUIRE(v->device >= 0 && v->device < 64, "device index out of range");
-            if (rec_cap[v->device] < need) {
-                if (rec_buf[v->device]) MQR_CHECK_HIP(hipFree(rec_buf[v->device]));
-                rec_buf[v->device] = nullptr;
-                rec_cap[v->device] = 0;
-                MQR_CHECK_HIP(hipMalloc(&rec_buf[v->device], need));
-                rec_cap[v->device] = need;
-            }
-            uint2* recs = static_cast<uint2*>(rec_buf[v->device]);
-            hipLaunchKernelGGL(k_tile_records, dim3((unsigned)((TW * TH + 7) / 8), (unsigned)nframes), dim3(256), 0, s,
-                               depths, HW, H, W, depth_frame, depth_max, TW, TH, recs);
-            auto tp = [&](auto kern) {
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(512), 0, s, list, lmask, counters, v->list_cap, t, v->pool,
-                                   v->voxel_size, depths, HW, H, W, fp, depth_frame, depth_max, sdf_trunc, first_new,
-                                   recs, TW, TH);
-            };
-            if (var == 45) tp(k_integrate_tp<7>);
-            else if (var == 46) tp(k_integrate_tp<6>);
-            else if (var == 47) tp(k_integrate_tp<7, 1>);
-            else if (var == 48) tp(k_integrate_tp<5, 1>);
-            else if (var == 49) tp(k_integrate_tp<7, 0, 1>);
-            else tp(k_integrate_tp<7, 1, 1>);
-            break;
-        }
-        // round 6: register-pressure forms of the default (k_integrate_wx<WPE, MODE>: MODE 1 halves, 2 fix-up launch)
-        case 51: wx(k_integrate_wx<6, 0>); break;
-        case 52: wx(k_integrate_wx<7, 1>); break;
-        case 53: wx(k_integrate_wx<8, 1>); break;
-        case 54: wx(k_integrate_wx<6, 1>); break;
-        case 55: *fixup = true; wx(k_integrate_wx<7, 2>); break;
-        case 56: *fixup = true; wx(k_integrate_wx<6, 2>); break;
-        case 57: *fixup = true; wx(k_integrate_wx<8, 3>); break;
-        case 58: *fixup = true; wx(k_integrate_wx<7, 3>); break;
-        case 59: *fixup = true; wx(k_integrate_wx<8, 2>); break;
-        case 60: wx(k_integrate_wx<7, 4>); break;  // the default + a workgroup barrier per frame
-        case 61: wx(k_integrate_wx<6, 4>); break;
-        case 62: *fixup = true; wx(k_integrate_wx<8, 6>); break;
-        case 65: case 66: case 67: {  // the default's kernel with OPT 1 / 2 / 3 (k_integrate_wt<7, DIV1, OPT>)
-            const int tcount = (int)v->launch_wbound;
-            const bool one = v->div1 && strunc_one_correction_ok(sdf_trunc);
-            auto kern = var == 65 ? (one ? k_integrate_wt<7, 1, 1> : k_integrate_wt<7, 0, 1>)
-                      : var == 66 ? (one ? k_integrate_wt<7, 1, 2> : k_integrate_wt<7, 0, 2>)
-                                  : (one ? k_integrate_wt<7, 1, 3> : k_integrate_wt<7, 0, 3>);
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), sizeof(float2) * (size_t)tcount, s, list, lmask, bad_out,
-                               counters, v->list_cap, t, v->pool, v->voxel_size, depths, HW, H, W, fp, depth_frame,
-                               depth_max, sdf_trunc, first_new, tcount);
-            *fixup = true;
-            break;
-        }
-        case 64: {  // the default's LDS-table kernel at >= 6 waves per SIMD (k_integrate_wt<6>)
-            const int tcount = (int)v->launch_wbound;
-            hipLaunchKernelGGL(k_integrate_wt<6>, dim3(grid), dim3(512), sizeof(float2) * (size_t)tcount, s, list, lmask,
-                               bad_out, counters, v->list_cap, t, v->pool, v->voxel_size, depths, HW, H, W, fp,
-                               depth_frame, depth_max, sdf_trunc, first_new, tcount);
-            *fixup = true;
-            break;
-        }
-        default: set_error("integrate variant " + std::to_string(var) + " unknown"); return 2;
-    }
-    return 0;
-}
-#endif
 
 // Host twin of den_unsafe(): true unless 2^-60 <= |x| <= 2^60.
 static bool div_unsafe_host(float x) {
@@ -527,14 +368,8 @@ static int resolve_pool_overflow(mqr_vbg* v, int p, bool* table_full = nullptr) 
 // integrate of the batch reads (k_gate's work; launch_integrate then launches no gate).
 static int enqueue_lpt(mqr_vbg* v, int p, int nframes) {
     bmask_t* om = reinterpret_cast<bmask_t*>(v->lpt[p] + v->list_cap);
-#if MQR_AB
-    if (v->xcd_order)
-        hipLaunchKernelGGL(k_xcd_order, dim3(1), dim3(1024), 0, v->stream, v->lists[p], v->ctr(p), v->list_cap,
-                           v->table(p), v->lpt[p], om, reinterpret_cast<uint8_t*>(om + v->list_cap));
-    else
-#endif
-        hipLaunchKernelGGL(k_lpt_order, dim3(1), dim3(1024), 0, v->stream, v->lists[p], v->ctr(p), v->list_cap,
-                           v->table(p).mask, v->lpt[p], om, v->shadow(p), nframes);
+    hipLaunchKernelGGL(k_lpt_order, dim3(1), dim3(1024), 0, v->stream, v->lists[p], v->ctr(p), v->list_cap,
+                       v->table(p).mask, v->lpt[p], om, v->shadow(p), nframes);
     MQR_CHECK_HIP(hipGetLastError());
     v->lpt_ready[p] = true;
     return 0;
@@ -559,7 +394,7 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
     // The host has just read this batch's counters (resolve_pool_overflow waits for them), so the
     // touch -- and an order enqueued behind it -- completed: integrate needs no device-side wait on
     // the touch stream, only for an order enqueued here, after that read.
-    bool touch_wait = v->touch_wait;
+    bool touch_wait = false;
     bool gated_by_order = false;  // k_lpt_order filled the shadow counters (no k_gate launch)
     if (v->lpt_order && n > 1) {  // on the touch stream: overlaps the previous integrate
         if (!v->lpt_ready[p]) {
@@ -568,13 +403,9 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
         }
         list = v->lpt[p];
         lmask = reinterpret_cast<bmask_t*>(v->lpt[p] + v->list_cap);
-        gated_by_order = !v->xcd_order;
+        gated_by_order = true;
     }
     v->lpt_ready[p] = false;
-    // the lean kernels run k_xcd_order's groups on the workgroups that share an XCD
-    [[maybe_unused]] const int grouped = (v->xcd_order && lmask) ? 1 : 0;
-    [[maybe_unused]] const unsigned lean_grid =
-        grouped ? (unsigned)(kNumGroups * std::min<int64_t>((3 * n / 2 + kNumGroups - 1) / kNumGroups, 1024)) : grid;
     if (v->pipelined && (touch_wait || spec > 0)) {
         MQR_CHECK_HIP(hipEventRecord(v->touch_ev(p), v->stream));
         MQR_CHECK_HIP(hipStreamWaitEvent(s, v->touch_ev(p), 0));
@@ -597,42 +428,26 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
     // must stay past 4HW for out-of-image voxels.  Otherwise the exact k_integrate_t runs alone.
     const bool lean_ok = !div_unsafe_host(sdf_trunc) && depth_scale == 1.0f && 4 * (HW + W) <= (int64_t{1} << 31);
     // Variants (mqr_vbg_set_variant, low byte; all bit-identical, tests/test_gpu_numerics.py):
-    //   0 default -- R = 16: k_integrate_win (brick map, 8-byte window depth reads, >= 7 waves per SIMD,
-    //     blocks outside the proven ranges redone in-kernel) when the frames allow the window reads (even
-    //     H W, 8-byte aligned stack), else variant 4;  R = 8: k_integrate_lean, plate map, dword gathers;
+    //   0 default -- R = 16, frames that allow 8-byte window depth reads (even H W, 8-byte aligned stack):
+    //     k_integrate_wt (brick map, window reads, the update through an LDS weight table, >= 7 waves per
+    //     SIMD, + the exact fix-up launch) while the volume's weight bound is known and its table fits,
+    //     else k_integrate_win (the same loop without the table, blocks outside the proven ranges redone
+    //     in-kernel);  other frames, and R = 8: variant 4;
     //   1 generic k_integrate (runtime R);  2 exact k_integrate_t;  4 k_integrate_lean with dword gathers
-    //     at >= 8 waves per SIMD (the round-2 default) + the exact fix-up launch;
-    //   A/B library only (MQR_AB, vbg_ab.hpp; DESIGN.md §4.1 has the measurements): 3 plate map;  5 packed
-    //     LDS tiles (k_integrate_lt);  6 / 7 paired-lane gathers;  8 VALU-lean projection / update, 9 + zc
-    //     checked per block, 10 + one-correction s / trunc;  11 / 12 / 14 / 19 16-byte windows;  13 / 16 /
-    //     17 / 18 / 20 / 21 / 22 8-byte windows at 6 waves / SIMD, with the block zc check, one-correction
-    //     division, ILP 4, in two halves;  15 = the round-3 default (the exact path in a fix-up launch);
-    //     23 = the round-4 default (k_integrate_lean_ab with the same arithmetic as 0);  24-31 the frame
-    //     loop software-pipelined / 1024-thread workgroups (k_integrate_win_ab);  32-35 timing diagnostics
-    //     (wrong results);  36-39 packed FP32 (k_integrate_pk);  40-43 branch-free window offsets / updates;  44 the
-    //     round-4 source;  45 / 46 lane-level tile proofs (k_tile_records + k_integrate_tp, >= 7 / 6 waves), 47 / 48 with
-    //     the eight record loads issued first (>= 7 / 5 waves), 49 / 50 = 45 / 47 branch-free.  (24 of round 4, a ballot skip of
-    //     out-of-image wave slots, ran 0.70 vs 0.48 ms per launch: removed.)
-    int var = v->kernel_variant;
-    if (var < 0 || var > 67 || var == 63) var = 0;
-    // the LDS-table kernels (default, 64) need a known weight bound whose table fits a workgroup's LDS share
-    const bool rtab_ok = v->rtab && v->launch_wbound >= 1 && v->launch_wbound <= kRtabMax;
-    if (var >= 64 && !rtab_ok) var = 0;
-    if (!MQR_AB && var != 1 && var != 2 && var != 4) var = 0;
-    if (var != 1 && var != 2 && !lean_ok) var = 2;
-    if (var == 5 && (v->R != 16 || W % 4 != 0 || W < 4 || (reinterpret_cast<uintptr_t>(depths) & 15))) var = 0;
-    if (var >= 5 && v->R != 16) var = 0;
+    //     (R = 16: brick map at >= 8 waves per SIMD, the round-2 default;  R = 8: plate map) + the exact
+    //     fix-up launch.
+    // The kernels that lost their measurement are recorded in DESIGN.md §4.1.
     // window reads: 4HW a multiple of the window and a frame base aligned to it, so an in-image
     // window never crosses the end of a frame and an out-of-image one (at 4HW) lies wholly past it
     const bool win8_ok = (HW % 2) == 0 && (reinterpret_cast<uintptr_t>(depths) & 7) == 0;
-    const bool win16_ok = (HW % 4) == 0 && (reinterpret_cast<uintptr_t>(depths) & 15) == 0;
-    if ((var == 11 || var == 12 || var == 14 || var == 19) && !win16_ok) var = 0;
+    // the LDS-table kernel needs a known weight bound whose table fits a workgroup's LDS share
+    const bool rtab_ok = v->rtab && v->launch_wbound >= 1 && v->launch_wbound <= kRtabMax;
+    int var = v->kernel_variant;  // 0, 1, 2 or 4
+    if (var != 1 && !lean_ok) var = 2;
     if (var == 0 && !(v->R == 16 && win8_ok)) var = 4;
-    if (var >= 13 && !win8_ok) var = 4;
-    if (v->R != 16 && v->R != 8) var = 1;
+    if (v->R != 16 && v->R != 8) var = 1;  // the templated kernels are built for R = 16 and 8
     v->last_var = var;
-    v->last_kname = var == 1 ? "k_integrate" : var == 2 ? "k_integrate_t" : var == 4 || v->R == 8 ? "k_integrate_lean"
-                                                                                                   : "k_integrate_ab";
+    v->last_kname = var == 1 ? "k_integrate" : var == 2 ? "k_integrate_t" : "k_integrate_lean";  // (0: below)
     const int32_t* bad_list = v->bad[p];
     const bmask_t* bad_mask = reinterpret_cast<const bmask_t*>(v->bad[p] + v->list_cap);
     int* bad_count = counters + kBadCount;
@@ -650,7 +465,7 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
                                v->bad[p], counters, v->list_cap, t, v->pool, v->voxel_size, depths, HW, H, W, fp,
                                depth_frame, depth_max, sdf_trunc, first_new);
             fixup = true;
-        } else if (var == 0 && rtab_ok) {  // the update through the (w, 1 / (w + 1)) table
+        } else if (rtab_ok) {  // the update through the (w, 1 / (w + 1)) table
             const int tcount = (int)v->launch_wbound;
             // s / sdf_trunc with one correction where that is verified exact for this sdf_trunc (bit 27: never)
             const bool one = v->div1 && strunc_one_correction_ok(sdf_trunc);
@@ -660,17 +475,11 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
                                counters, v->list_cap, t, v->pool, v->voxel_size, depths, HW, H, W, fp, depth_frame,
                                depth_max, sdf_trunc, first_new, tcount);
             fixup = true;
-        } else if (var == 0) {
+        } else {
             v->last_kname = "k_integrate_win<7>";
             hipLaunchKernelGGL(k_integrate_win<7>, dim3(grid), dim3(512), 0, s, list, lmask, counters, v->list_cap, t,
                                v->pool, v->voxel_size, depths, HW, H, W, fp, depth_frame, depth_max, sdf_trunc,
                                first_new);
-        } else {
-#if MQR_AB
-            if (launch_integrate_ab(v, var, s, grid, lean_grid, grouped, list, lmask, counters, t, depths, HW, H, W, fp,
-                                    depth_frame, depth_max, sdf_trunc, first_new, v->bad[p], &fixup, nframes))
-                return 1;
-#endif
         }
     } else {  // R == 8
         if (var == 2) {
@@ -859,9 +668,7 @@ static int touch_batch_launch(mqr_vbg* v, int p, const float* dbase, int64_t HW,
                               float depth_scale, float depth_max, float sdf_trunc, float block_size, int64_t max_touch,
                               TouchState& ts) {
     ts.worst = v->pool_count + b * max_touch;
-    const int64_t headroom = v->table_worst ? b * max_touch
-                                            : std::min<int64_t>(b * max_touch,
-                                                                std::max<int64_t>(kMinHeadroom, 4 * v->batch_new_max));
+    const int64_t headroom = std::min<int64_t>(b * max_touch, std::max<int64_t>(kMinHeadroom, 4 * v->batch_new_max));
     if (ensure_table(v, std::max(kMinTableLive, v->pool_count + headroom))) return 1;
     ts.limited = v->probe_one || v->tab.cap < next_pow2(2 * ts.worst);
     ts.pool_before = v->pool_count;
@@ -920,7 +727,7 @@ int mqr_version(void) { return 100; }
 int mqr_build_tag(int which, char* buf, int cap) {
     MQR_REQUIRE(buf && cap > 0, "null argument");
     MQR_REQUIRE(which == 0 || which == 1, "which: 0 = integrate sources, 1 = confidence sources");
-    const std::string t = which == 0 ? std::string(MQR_AB ? "ab-" : "") + MQR_SRC_TAG : std::string(confidence_src_tag());
+    const std::string t = which == 0 ? std::string(MQR_SRC_TAG) : std::string(confidence_src_tag());
     std::snprintf(buf, (size_t)cap, "%s", t.c_str());
     return 0;
 }
@@ -1561,12 +1368,15 @@ int mqr_vbg_unpack_weighted(mqr_vbg* v, const int32_t* union_keys, int64_t U, co
 
 int mqr_vbg_set_variant(mqr_vbg* v, int variant) {
     MQR_REQUIRE(v, "null volume");
-    if (sync_all(v)) return 1;
-    if (!MQR_AB && (((variant & 0xff) != 0 && (variant & 0xff) != 1 && (variant & 0xff) != 2 && (variant & 0xff) != 4) || (variant & 0x8000))) {
-        set_error("integrate variant " + std::to_string(variant) + " is an A/B kernel: only in tools/_ab/libmqr_ab.so (make ab)");
+    // checked before anything is applied: a rejected value leaves the configuration as it was
+    const int kernel = variant & 0xff;
+    if ((kernel != 0 && kernel != 1 && kernel != 2 && kernel != 4) || (variant & 0xe000)) {
+        set_error("integrate variant " + std::to_string(variant) +
+                  ": the low byte selects kernel 0, 1, 2 or 4, and bits 13-15 are retired");
         return 1;
     }
-    v->kernel_variant = variant & 0xff;
+    if (sync_all(v)) return 1;
+    v->kernel_variant = kernel;
     v->pipelined = (variant & 0x100) == 0;  // bit 8: serialise touch and integrate (A/B of the overlap)
     // (the integrate stream rather than the touch stream at the device's highest priority measured
     // 2.592 vs 2.587 ms per step: removed)
@@ -1579,9 +1389,6 @@ int mqr_vbg_set_variant(mqr_vbg* v, int variant) {
     v->first_batch_frames = (variant & 0x200000) ? 64 : (variant & 0x400000) ? 32 : (variant & 0x800000) ? 16 : kFirstBatch;
     v->sys_fence = (variant & 0x800) != 0;  // bit 11: system-scope ordering / timing events (A/B)
     v->probe_one = (variant & 0x1000) != 0; // bit 12: force the full-table retry path (test hook)
-    v->table_worst = (variant & 0x2000) != 0; // bit 13: size the table for the worst case (round-2 A/B)
-    v->touch_wait = (variant & 0x4000) != 0;  // bit 14: integrate always waits on a touch-stream event (A/B)
-    v->xcd_order = (variant & 0x8000) != 0;   // bit 15: spatial per-XCD groups (k_xcd_order, A/B)
     v->touch_ppt = (variant & 0x10000) ? 1 : 2;  // bit 16: one stride-4 pixel per touch thread (A/B)
     v->spec_head = (variant & 0x40000) == 0;     // bit 18: no speculative first-batch integrate (A/B)
     v->async_return = (variant & 0x1000000) == 0; // bit 24: integrate_frames drains its streams before returning (A/B)

@@ -1,12 +1,6 @@
 // vbg_kernels.hpp -- device code of the TSDF volume (included once, by vbg.hip).
 // Open3D 0.19 VoxelBlockGrid semantics; float32 with no FMA contraction.
 #pragma once
-#ifndef MQR_DIAG
-#define MQR_DIAG 0  // 1 / 2: timing-only builds of the lean kernel, 3 / 4 / 5 of the tile kernels (wrong results; never shipped)
-#endif
-#ifndef MQR_AB
-#define MQR_AB 0  // 1: the A/B kernels of vbg_ab.hpp (tools/_ab/libmqr_ab.so only)
-#endif
 #include <climits>
 
 #include "mqr_common.hpp"
@@ -646,11 +640,7 @@ __device__ __forceinline__ void lean_gather(float (&dv)[ZPER], bool& bad, const 
         const bool in = (v >= 0) & (u >= 0) & (v <= hm1) & (u <= wm1);
         // out of the image: row H (byte offset H W4 = 4HW, past the end of the frame)
         const uint32_t off = in ? __umul24((uint32_t)(int)v, W4) + ((uint32_t)(int)u << 2) : __umul24((uint32_t)hf, W4);
-#if MQR_DIAG == 1  // timing diagnostics only (tools/diag_integrate.sh): projection without the gather
-        dv[k] = zc + (float)(off & 1u) * 1e-30f;
-#else
         dv[k] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, 0));
-#endif
         // keep each group of ILP voxels' projections next to their loads: hoisting all projections
         // above the loads (the scheduler's choice) keeps ~6 more VGPRs per voxel live and halves the
         // occupancy; ILP > 1 lets the scheduler interleave that many independent chains
@@ -664,11 +654,6 @@ __device__ __forceinline__ void lean_update(float2 (&tw)[ZPER], const float (&dv
                                             const float (&xs)[ZPER], const float (&ys)[ZPER],
                                             const float (&zs)[ZPER], float depth_max, float sdf_trunc, float y1t) {
     const float e8 = fp.ext[8], e9 = fp.ext[9], e10 = fp.ext[10], e11 = fp.ext[11];
-#if MQR_DIAG == 2  // timing diagnostics only: the gather without the update
-#pragma unroll
-    for (int k = 0; k < ZPER; ++k) tw[k].x += dv[k];
-    return;
-#endif
 #pragma unroll
     for (int k = 0; k < ZPER; ++k) {
         const float az = xs[k] * e8 + ys[k] * e9;
@@ -689,15 +674,15 @@ __device__ __forceinline__ void lean_update(float2 (&tw)[ZPER], const float (&dv
     }
 }
 
-// ---- window gathers (PAIR = 4: 16-byte, 5: 8-byte windows) ------------------------------------------
-// Each lane loads the aligned 16- (8-) byte window holding its pixel and keeps its dword.  Lanes whose
-// pixels share a window issue the same address, which the L1 serves once: in tools/gather_ceiling
-// the brick map's 64-lane 16-byte window load costs half a 64-lane dword gather of the same pixels
-// (6.9 vs 13.6 ns per instruction per CU).  The frame base must be 16- (8-) byte aligned and 4HW a
-// multiple of the window (host): then an in-image window never crosses the end of the frame, and an
-// out-of-image lane's window at 4HW is wholly past the end (reads 0).
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-template <int ZPER, int ILP = 1, int WIN = 16, bool ZCHK = true, int K0 = 0, int K1 = ZPER, int DIAGV = 0>
+// ---- window gathers ------------------------------------------------------------------------------------
+// Each lane loads the aligned 8-byte window holding its pixel and keeps its dword.  Lanes whose pixels
+// share a window issue the same address, which the L1 serves once: in tools/gather_ceiling the brick
+// map's 64-lane 16-byte window load costs half a 64-lane dword gather of the same pixels (6.9 vs 13.6 ns
+// per instruction per CU; 16-byte windows cost registers and lost to 8-byte ones in the kernel, DESIGN.md
+// §4.1).  The frame base must be 8-byte aligned and 4HW a multiple of the window (host): then an in-image
+// window never crosses the end of the frame, and an out-of-image lane's window at 4HW is wholly past the
+// end (reads 0).  Two voxel chains at a time, as lean_gather<ZPER, 2>.
+template <int ZPER>
 __device__ __forceinline__ void lean_gather_w(float (&dv)[ZPER], bool& bad, const FrameParams& fp,
                                               __amdgpu_buffer_rsrc_t rs, const float (&xs)[ZPER],
                                               const float (&ys)[ZPER], const float (&zs)[ZPER], uint32_t W4,
@@ -707,82 +692,51 @@ __device__ __forceinline__ void lean_gather_w(float (&dv)[ZPER], bool& bad, cons
     for (int j = 0; j < 12; ++j) e[j] = fp.ext[j];
     const float fx = fp.fx, fy = fp.fy, cx = fp.cx, cy = fp.cy;
 #pragma unroll
-    for (int k = K0; k < K1; ++k) {
+    for (int k = 0; k < ZPER; ++k) {
         const float ax = xs[k] * e[0] + ys[k] * e[1];
         const float ay = xs[k] * e[4] + ys[k] * e[5];
         const float az = xs[k] * e[8] + ys[k] * e[9];
         const float xc = (ax + zs[k] * e[2]) + e[3];
         const float yc = (ay + zs[k] * e[6]) + e[7];
         const float zc = (az + zs[k] * e[10]) + e[11];
-        if (ZCHK) bad |= (__float_as_uint(zc) - 0x2D800000u) > 0x30000000u;  // not 2^-36 <= zc <= 2^60
-        // DIAGV (A/B library only): bit 0 = timing diagnostics (wrong results): the bare v_rcp; bit 1 = the
-        // in-image offset computed for every lane and selected.  The default form lets the compiler branch
-        // around the offset of out-of-image lanes: 0.595-0.603 vs 0.638-0.647 ms per launch for a form it
-        // compiled without those branches (profiles/r05_ab_integrate_branchfree.json, variant 44 vs 0).
-        const float inv_z = (DIAGV & 1) ? __builtin_amdgcn_rcpf(zc) : rcp_m(zc);
+        bad |= (__float_as_uint(zc) - 0x2D800000u) > 0x30000000u;  // not 2^-36 <= zc <= 2^60
+        const float inv_z = rcp_m(zc);
         const float u = fx * xc * inv_z + cx;
         const float v = fy * yc * inv_z + cy;
         const bool in = (__float_as_uint(v) <= hm1_bits) && (__float_as_uint(u) <= wm1_bits);
-        uint32_t off;
-        if constexpr ((DIAGV & 2) != 0) {
-            uint32_t off_in = __umul24((uint32_t)(int)v, W4) + ((uint32_t)(int)u << 2);
-            asm volatile("" : "+v"(off_in));
-            off = in ? off_in : past_end;
-        } else {
-            off = in ? __umul24((uint32_t)(int)v, W4) + ((uint32_t)(int)u << 2) : past_end;
-        }
-        if constexpr (WIN == 16) {
-            const u32x4 q = __builtin_amdgcn_raw_buffer_load_b128(rs, off & ~15u, 0, 0);
-            const uint32_t lo = (off & 8u) ? q.z : q.x, hi = (off & 8u) ? q.w : q.y;
-            dv[k] = __uint_as_float((off & 4u) ? hi : lo);
-        } else {
-            const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs, off & ~7u, 0, 0);
-            dv[k] = __uint_as_float((off & 4u) ? q.y : q.x);
-        }
-        if ((k + 1) % ILP == 0) __builtin_amdgcn_sched_barrier(0);
+        // This form lets the compiler branch around the offset of out-of-image lanes: 0.595-0.603 vs
+        // 0.638-0.647 ms per launch for a form it compiled without those branches
+        // (profiles/r05_ab_integrate_branchfree.json).
+        const uint32_t off = in ? __umul24((uint32_t)(int)v, W4) + ((uint32_t)(int)u << 2) : past_end;
+        const u32x2 q = __builtin_amdgcn_raw_buffer_load_b64(rs, off & ~7u, 0, 0);
+        dv[k] = __uint_as_float((off & 4u) ? q.y : q.x);
+        if ((k + 1) % 2 == 0) __builtin_amdgcn_sched_barrier(0);
     }
 }
 
-// DIV1: s / sdf_trunc with one Markstein correction (the host enables it only for an sdf_trunc whose
-// every s in [0, sdf_trunc] it verified against IEEE division, strunc_one_correction_ok; the
-// sequence is odd in s, so negative s follow).
-template <int ZPER, int ILP = 1, int DIV1 = 0, int K0 = 0, int K1 = ZPER, int DIAGV = 0>
+// The running-average update behind lean_gather_w, branching per voxel (selecting instead lost).
+template <int ZPER>
 __device__ __forceinline__ void lean_update_v(float2 (&tw)[ZPER], const float (&dv)[ZPER], const FrameParams& fp,
                                               const float (&xs)[ZPER], const float (&ys)[ZPER],
                                               const float (&zs)[ZPER], float depth_max, float sdf_trunc, float y1t) {
     const float e8 = fp.ext[8], e9 = fp.ext[9], e10 = fp.ext[10], e11 = fp.ext[11];
 #pragma unroll
-    for (int k = K0; k < K1; ++k) {
+    for (int k = 0; k < ZPER; ++k) {
         const float az = xs[k] * e8 + ys[k] * e9;
         const float zc = (az + zs[k] * e10) + e11;
         const float d = dv[k];
         const float sdf = d - zc;
-        if constexpr ((DIAGV & 4) == 0) {
-            if (!(d <= 0) && !(d > depth_max) && !(sdf < -sdf_trunc)) {
-                float s;
-                asm("v_min_f32 %0, %1, %2" : "=v"(s) : "s"(sdf_trunc), "v"(sdf));
-                const float q0 = s * y1t;
-                const float q1 = (DIAGV & 1) ? q0 : __builtin_fmaf(__builtin_fmaf(-sdf_trunc, q0, s), y1t, q0);
-                const float sn = DIV1 || (DIAGV & 1) ? q1 : __builtin_fmaf(__builtin_fmaf(-sdf_trunc, q1, s), y1t, q1);
-                const float wgt = tw[k].y, wp = wgt + 1;
-                tw[k].x = (wgt * tw[k].x + sn) * ((DIAGV & 1) ? __builtin_amdgcn_rcpf(wp) : rcp_m(wp));
-                tw[k].y = wp;
-            }
-        } else {  // DIAGV bit 2 (A/B library only): every lane evaluates the update and selects (no branch)
-            const bool up = !(d <= 0) && !(d > depth_max) && !(sdf < -sdf_trunc);
+        if (!(d <= 0) && !(d > depth_max) && !(sdf < -sdf_trunc)) {
             float s;
             asm("v_min_f32 %0, %1, %2" : "=v"(s) : "s"(sdf_trunc), "v"(sdf));
-            const float q0 = s * y1t;
-            const float q1 = (DIAGV & 1) ? q0 : __builtin_fmaf(__builtin_fmaf(-sdf_trunc, q0, s), y1t, q0);
-            const float sn = DIV1 || (DIAGV & 1) ? q1 : __builtin_fmaf(__builtin_fmaf(-sdf_trunc, q1, s), y1t, q1);
-            const float wgt = tw[k].y;
-            float wp = wgt + 1;
-            float nt = (wgt * tw[k].x + sn) * ((DIAGV & 1) ? __builtin_amdgcn_rcpf(wp) : rcp_m(wp));
-            asm volatile("" : "+v"(nt), "+v"(wp));
-            tw[k].x = up ? nt : tw[k].x;
-            tw[k].y = up ? wp : wgt;
+            const float q0 = s * y1t;  // s / sdf_trunc: div_rn_core with the reciprocal refinement hoisted
+            const float q1 = __builtin_fmaf(__builtin_fmaf(-sdf_trunc, q0, s), y1t, q0);
+            const float sn = __builtin_fmaf(__builtin_fmaf(-sdf_trunc, q1, s), y1t, q1);
+            const float wgt = tw[k].y, wp = wgt + 1;
+            tw[k].x = (wgt * tw[k].x + sn) * rcp_m(wp);
+            tw[k].y = wp;
         }
-        if ((k + 1) % ILP == 0) __builtin_amdgcn_sched_barrier(0);
+        if ((k + 1) % 2 == 0) __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -828,8 +782,8 @@ __host__ __device__ constexpr int lean_dz(int k) { return MAP == 1 ? 4 * (k & 3)
 // allocation must allow; ILP: voxel chains the scheduler may interleave.  A block whose operands leave
 // the proven ranges is handed to the exact fix-up launch behind the kernel (hand_off) unwritten; every
 // other block is written back whole.  (The round-2..4 variants of this kernel -- paired-lane gathers,
-// VALU-lean forms, 16-byte windows, block-level zc checks, XCD-grouped lists -- are A/B-only:
-// k_integrate_lean_ab in vbg_ab.hpp.)
+// VALU-lean forms, 16-byte windows, block-level zc checks, XCD-grouped lists -- were measured and
+// removed: DESIGN.md §4.1.)
 template <int R, int NT, int MAP = 0, int WPE = 1, int ILP = 1>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_integrate_lean(
     const int32_t* __restrict__ list, const bmask_t* __restrict__ lmask, int32_t* __restrict__ bad_out,
@@ -910,8 +864,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(WPE, 8))) vo
 // operands leave the proven ranges is redone by the workgroup itself through the exact path
 // (exact_block_call, not inlined: its registers stay out of the frame loop's allocation).  >= 7 waves per
 // SIMD (three per-block address words spill to scratch outside the frame loop).  Bit-identical to the
-// generic kernel (tests/test_gpu_numerics.py).  Measured alternatives, all A/B-only (vbg_ab.hpp,
-// DESIGN.md §4.1): the frame loop software-pipelined (whole frames or half frames), 1024-thread
+// generic kernel (tests/test_gpu_numerics.py).  Measured alternatives, all removed since (DESIGN.md
+// §4.1): the frame loop software-pipelined (whole frames or half frames), 1024-thread
 // workgroups, packed FP32 arithmetic -- none faster.
 template <int NT>
 __host__ __device__ constexpr int win_dy(int k) { return NT == 512 ? 8 * (k >> 2) : 0; }
@@ -967,9 +921,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
                 const int f = bm_ctz(m);
                 m &= m - 1;
                 float dv[ZPER];
-                lean_gather_w<ZPER, 2, 8>(dv, bad, fps[f], frame_rsrc(depths + depth_frame[f] * HW, bytes), xs, ys, zs,
-                                          W4, bytes, hb, wb);
-                lean_update_v<ZPER, 2, 0>(tw, dv, fps[f], xs, ys, zs, depth_max, sdf_trunc, y1t);
+                lean_gather_w<ZPER>(dv, bad, fps[f], frame_rsrc(depths + depth_frame[f] * HW, bytes), xs, ys, zs, W4,
+                                    bytes, hb, wb);
+                lean_update_v<ZPER>(tw, dv, fps[f], xs, ys, zs, depth_max, sdf_trunc, y1t);
             }
             if (__syncthreads_or(bad)) {  // block-uniform: the exact path redoes it from the pool
                 exact_block_call<R, NT>(pool + (int64_t)buf * R3, buf >= first_new, mask, xb, yb, zb, voxel_size, depths,
@@ -999,11 +953,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
 constexpr int kRtabMax = 6000;  // table entries: 48 KB of LDS, 3 workgroups per CU still fit
 
 // DIV1: s / sdf_trunc with one Markstein correction (host: strunc_one_correction_ok verified it for this
-// sdf_trunc over every s in [-t, t]), as lean_update_v<DIV1>.  OPT (A/B library only): bit 0 keeps the table
-// entries' LDS addresses themselves (no base add per read), bit 1 selects the pixel's dword of its 8-byte
-// window by one 64-bit shift (v_lshrrev_b64 by 8 * the byte offset; the shifter takes its low 6 bits).
-typedef __attribute__((address_space(3))) const float2 lds_float2;
-template <int WPE, int DIV1 = 0, int OPT = 0>
+// sdf_trunc over every s in [-t, t]; the sequence is odd in s, so negative s follow), else with two as
+// lean_update_v.
+template <int WPE, int DIV1>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void k_integrate_wt(
     const int32_t* __restrict__ list, const bmask_t* __restrict__ lmask, int32_t* __restrict__ bad_out,
     int* __restrict__ counters, int64_t list_cap,
@@ -1026,7 +978,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
     const int vx = (l & 7) + 8 * (w & 1), vy = ((l >> 3) & 1) + 2 * (w >> 1), vz = l >> 4;
     const uint32_t voff = 8u * (uint32_t)(vx + R * vy + R2 * vz);
     const char* tbase = reinterpret_cast<const char*>(rtab);
-    const uint32_t lbase = (OPT & 1) ? (uint32_t)(uintptr_t)(lds_float2*)rtab : 0u;  // LDS address of entry 0
     for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
         const int32_t slot = list[i];
         const int buf = __builtin_amdgcn_readfirstlane(t.vals[slot]);
@@ -1052,68 +1003,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
                 zs[k] = (float)(zb * R + vz + dz) * voxel_size;
                 bad |= !(tw.y >= 0.0f && tw.y <= wlim && tw.y == __builtin_truncf(tw.y));
                 ts[k] = tw.x;
-                wa[k] = lbase + 8u * (uint32_t)(bad ? 0.0f : tw.y);
+                wa[k] = 8u * (uint32_t)(bad ? 0.0f : tw.y);
             }
             bmask_t m = mask;
             while (m) {
                 const int f = bm_ctz(m);
                 m &= m - 1;
                 float dv[ZPER];
-                u32x2 qv[ZPER];
-                uint32_t shv[ZPER];
-                if constexpr ((OPT & 2) != 0) {  // lean_gather_w<ZPER, 2, 8>'s operations, the window kept whole
-                    const FrameParams& g = fps[f];
-                    const __amdgpu_buffer_rsrc_t rs = frame_rsrc(depths + depth_frame[f] * HW, bytes);
-                    float e[12];
-#pragma unroll
-                    for (int j = 0; j < 12; ++j) e[j] = g.ext[j];
-#pragma unroll
-                    for (int k = 0; k < ZPER; ++k) {
-                        const float ax = xs[k] * e[0] + ys[k] * e[1];
-                        const float ay = xs[k] * e[4] + ys[k] * e[5];
-                        const float az = xs[k] * e[8] + ys[k] * e[9];
-                        const float xc = (ax + zs[k] * e[2]) + e[3];
-                        const float yc = (ay + zs[k] * e[6]) + e[7];
-                        const float zc = (az + zs[k] * e[10]) + e[11];
-                        bad |= (__float_as_uint(zc) - 0x2D800000u) > 0x30000000u;
-                        const float inv_z = rcp_m(zc);
-                        const float u = g.fx * xc * inv_z + g.cx;
-                        const float v = g.fy * yc * inv_z + g.cy;
-                        const bool in = (__float_as_uint(v) <= hb) && (__float_as_uint(u) <= wb);
-                        const uint32_t off = in ? __umul24((uint32_t)(int)v, W4) + ((uint32_t)(int)u << 2) : bytes;
-                        qv[k] = __builtin_amdgcn_raw_buffer_load_b64(rs, off & ~7u, 0, 0);
-                        shv[k] = off << 3;
-                        if ((k + 1) % 2 == 0) __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else {
-                    lean_gather_w<ZPER, 2, 8>(dv, bad, fps[f], frame_rsrc(depths + depth_frame[f] * HW, bytes), xs, ys,
-                                              zs, W4, bytes, hb, wb);
-                }
+                lean_gather_w<ZPER>(dv, bad, fps[f], frame_rsrc(depths + depth_frame[f] * HW, bytes), xs, ys, zs, W4,
+                                    bytes, hb, wb);
                 const FrameParams& fp = fps[f];
                 const float e8 = fp.ext[8], e9 = fp.ext[9], e10 = fp.ext[10], e11 = fp.ext[11];
 #pragma unroll
                 for (int k = 0; k < ZPER; ++k) {
                     const float az = xs[k] * e8 + ys[k] * e9;
                     const float zc = (az + zs[k] * e10) + e11;
-                    float d;
-                    if constexpr ((OPT & 2) != 0) {
-                        uint64_t r;
-                        const uint64_t q64 = ((uint64_t)qv[k].y << 32) | qv[k].x;
-                        asm("v_lshrrev_b64 %0, %1, %2" : "=v"(r) : "v"(shv[k]), "v"(q64));
-                        d = __uint_as_float((uint32_t)r);
-                    } else {
-                        d = dv[k];
-                    }
+                    const float d = dv[k];
                     const float sdf = d - zc;
                     if (!(d <= 0) && !(d > depth_max) && !(sdf < -sdf_trunc)) {
-                        // the entry read first: its LDS latency overlaps the quotient
-                        float2 e;  // (w, 1 / (w + 1))
-                        if constexpr ((OPT & 1) != 0) {
-                            lds_float2* px = (lds_float2*)(uintptr_t)wa[k];
-                            e = make_float2(px->x, px->y);
-                        } else {
-                            e = *reinterpret_cast<const float2*>(tbase + wa[k]);
-                        }
+                        // the entry (w, 1 / (w + 1)) read first: its LDS latency overlaps the quotient
+                        const float2 e = *reinterpret_cast<const float2*>(tbase + wa[k]);
                         float s;
                         asm("v_min_f32 %0, %1, %2" : "=v"(s) : "s"(sdf_trunc), "v"(sdf));
                         const float q0 = s * y1t;
@@ -1131,7 +1040,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
 #pragma unroll
                 for (int k = 0; k < ZPER; ++k)
                     pool_store(vox, voff, (R * win_dy<NT>(k) + R2 * win_dz<NT>(k)) * (int)sizeof(float2),
-                               make_float2(ts[k], (float)((wa[k] - lbase) >> 3)));
+                               make_float2(ts[k], (float)(wa[k] >> 3)));
             }
         }
         __syncthreads();
@@ -1153,7 +1062,7 @@ __global__ void k_check_rcp(int mode, uint32_t lo_bits, uint64_t count, uint32_t
     }
 }
 
-// One-correction quotient s / t of lean_update_v<DIV1 = 1> against IEEE division for every float s
+// One-correction quotient s / t of k_integrate_wt<.., 1> against IEEE division for every float s
 // with bits in [lo_bits, lo_bits + count) (the host passes [+0, t]).
 __global__ void k_check_strunc(float t, uint32_t lo_bits, uint64_t count, uint32_t* mismatches) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -45,19 +45,12 @@ def test_shortened_reciprocals_exact(which, lo, hi):
     assert mm == 0, f"mode {which}: {mm} mismatches, first bit pattern {first:#x}"
 
 
-# MQR_AB_TEST=1 (tests/test_gpu_ab_variants.py, with MQR_HIP_LIB = tools/_ab/libmqr_ab.so): the integrate
-# tests below also cover the A/B kernels the shipped library leaves out (variants 3 and 5, bit 0x8000)
-AB = os.environ.get("MQR_AB_TEST") == "1"
 # 0x10000: one pixel per touch thread, 0x40000: no speculative first-batch integrate, 0x100000: 64-frame
 # batches, 0x200000 / 0x400000 / 0x800000: a first batch of 64 / 32 / 16 frames, 0x4000000: the default
 # kernel without its LDS weight table (k_integrate_win)
 INTEGRATE_VARIANTS = {16: (0, 2, 4, 0x100, 0x104, 0x200, 0x400, 0x800, 0x10000, 0x40000, 0x100000, 0x200000,
                            0x400000, 0x800000, 0x4000000, 0x8000000),
                       8: (0, 2, 0x100)}
-if AB:
-    INTEGRATE_VARIANTS = {16: (0, 3, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25,
-                               26, 27, 28, 29, 30, 31, 36, 37, 38, 39, 40, 41, 44, 45, 46, 47, 48, 49, 50, 64, 0x4000000, 0x105, 0x605, 0x106, 0x108, 0x10b, 0x10d, 0x111, 0x8000, 0x8003, 0x8008, 0x800a, 0x800b, 0x800d, 0x8011), 8: (0, 0x8000)}
-
 
 def test_specialised_integrate_equals_generic():
     """Every integrate-kernel variant (lean default, LDS block-tiled, exact R-specialised; pipelined or
@@ -208,7 +201,7 @@ def test_fast_integrate_exact_fallback():
     for d in depth_mm:
         d[::7, ::5] = np.float32(1e-30)   # in-image, > 0, below 2^-60: exact division path
     out = []
-    cases = ((16, 1), (16, 0), (16, 2), (16, 6 if AB else 0x100), (8, 1), (8, 0), (8, 2))
+    cases = ((16, 1), (16, 0), (16, 2), (16, 0x100), (8, 1), (8, 0), (8, 2))
     for R, variant in cases:
         v = VoxelBlockGrid(voxel_size=0.01, block_resolution=R, block_count=64)
         _lib.call("mqr_vbg_set_variant", v.handle, variant)
@@ -248,10 +241,10 @@ def test_lean_integrate_exact_fallback():
     depths = [near] + [np.asarray(d, np.float32) for d in seq["depth"]]
     Ks = np.concatenate([seq["K"][:1], seq["K"]])
     Ts = np.concatenate([np.eye(4)[None], seq["T_wc"]])
-    # (the default redoes such blocks in-kernel; variant 4 and, in the A/B library, 15 hand them to the
-    # fix-up launch)
-    cases = ((16, 1), (16, 0), (16, 5 if AB else 0x200), (16, 2), (16, 0x100), (16, 9 if AB else 0x400),
-             (16, 8 if AB else 0x800), (16, 13 if AB else 0x100), (16, 17 if AB else 0x200), (16, 15 if AB else 4),
+    # (k_integrate_win redoes such blocks in-kernel; the default's LDS-table kernel and variant 4 hand them
+    # to the fix-up launch)
+    cases = ((16, 1), (16, 0), (16, 0x200), (16, 2), (16, 0x100), (16, 0x400),
+             (16, 0x800), (16, 0x100), (16, 0x200), (16, 4),
              (8, 1), (8, 0), (8, 2))
     out = []
     for R, variant in cases:
@@ -323,3 +316,28 @@ def test_weight_table_across_calls_and_unknown_bounds():
     for variant in (0, 0x4000000, 0x8000000):
         compare_volumes(out[1], out[variant], 0.0)
         compare_volumes(out[(1, "imported")], out[(variant, "imported")], 0.0)
+
+
+def test_retired_integrate_variants_rejected():
+    """The low byte of mqr_vbg_set_variant selects kernel 0, 1, 2 or 4 and bits 13-15 are retired: any other
+    value is refused with a message and leaves the volume on its configuration -- the integrate that follows
+    runs the default (mqr_vbg_last_kernel 0) and equals the generic kernel bit for bit."""
+    from gpu_helpers import compare_volumes
+    from mqr import _lib, synthetic
+    from mqr.vbg import VoxelBlockGrid
+    seq = synthetic.make_sequence("sphere", n=4, height=120, width=160, f=131.25, noise=True, seed=1)
+    kw = dict(depth_scale=1.0, depth_max=3.0, trunc_voxel_multiplier=4.0)
+    L = _lib.load()
+    ref = VoxelBlockGrid(voxel_size=0.02, block_resolution=16, block_count=64)
+    _lib.call("mqr_vbg_set_variant", ref.handle, 1)
+    ref.integrate_frames(seq["depth"], seq["K"], seq["T_wc"], **kw)
+    ref_out = ref.export()
+    for variant in (3, 5, 44, 64, 0x2000, 0x4000, 0x8000):
+        v = VoxelBlockGrid(voxel_size=0.02, block_resolution=16, block_count=64)
+        assert L.mqr_vbg_set_variant(v.handle, variant) != 0, hex(variant)
+        assert L.mqr_last_error().decode(errors="replace").strip(), hex(variant)
+        v.integrate_frames(seq["depth"], seq["K"], seq["T_wc"], **kw)
+        assert compare_volumes(ref_out, v.export(), 0.0) == 0.0, hex(variant)
+        last = ctypes.c_int(-1)
+        _lib.call("mqr_vbg_last_kernel", v.handle, ctypes.byref(last))
+        assert last.value == 0, (hex(variant), last.value)

@@ -20,7 +20,7 @@
 #   traffic     FETCH_SIZE / WRITE_SIZE passes (tools/pmc_traffic.sh) -> profiles/${TAG}_pmc_traffic.json
 #   pmcint      SQ / TA / TCP counters of the default integrate kernel (tools/pmc_ab.sh) -> profiles_new/
 #   pmcconf     counter passes of the confidence kernel (tools/pmc_conf.sh) -> profiles_new/${TAG}_pmc_confidence.json
-#   abint:V     tools/ab_integrate.py over integrate variants V (comma separated, A/B library)
+#   abint:V     tools/ab_integrate.py over integrate variants V (comma separated)
 #   abext:M     tools/ab_extract.py over extraction modes M (A/B library)
 #   d2h         device -> host copy ceilings (tools/d2h_probe.py) with 1 / 4 / 8 staging threads
 #   chunkab     drop-in integrate() with 64- vs 127-frame hand-offs (tools/dropin_ab.py)
@@ -139,7 +139,7 @@ for step in ${STEPS:-tests}; do
       rm -rf /tmp/pmcconf
       head -c 400 gpurun_out/pmc_conf.json ;;
     abint:*)
-      MQR_HIP_LIB="$PWD/tools/_ab/libmqr_ab.so" timeout -k 10 600 python -u tools/ab_integrate.py --check --rounds 7 --variants "${step#abint:}" \
+      timeout -k 10 600 python -u tools/ab_integrate.py --check --rounds 7 --variants "${step#abint:}" \
         > gpurun_out/${TAG}_abint.json 2> gpurun_out/${TAG}_abint.err || { tail -20 gpurun_out/${TAG}_abint.err; exit 1; }
       cat gpurun_out/${TAG}_abint.json ;;
     abext:*)

@@ -2,16 +2,16 @@
 # Counter comparison of integrate-kernel variants (one rocprofv3 --pmc pass per counter group and
 # variant, each under its own time limit) over tools/traffic_workload.py; per-launch means of the
 # kernels matching $KRE go to gpurun_out/pmc_ab.json.  Usage (on the box):
-#   VARIANTS="0 3" bash tools/pmc_ab.sh
+#   VARIANTS="0 4" bash tools/pmc_ab.sh
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-KRE="${KRE:-k_integrate_(wt|win|lean|lt|pk)}"
+KRE="${KRE:-k_integrate_(wt|win|lean)}"
 GROUPS_=("SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"
          "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INST_CYCLES_VMEM_RD TA_BUSY_avr TA_TA_BUSY_sum GRBM_GUI_ACTIVE"
          "TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_LATENCY_sum GRBM_GUI_ACTIVE")
-for v in ${VARIANTS:-0 3}; do
+for v in ${VARIANTS:-0 4}; do
   i=0
   for G in "${GROUPS_[@]}"; do
     i=$((i+1))

@@ -1,7 +1,7 @@
 #!/bin/bash
 # HBM traffic A/B of integrate variants: FETCH_SIZE and WRITE_SIZE passes of tools/traffic_workload.py
 # per variant (each pass under its own time limit), summarised by tools/pmc_summary.py into
-# gpurun_out/traffic_v<variant>.json.  Usage (on the box): VARIANTS="-1 32768" bash tools/traffic_ab.sh
+# traffic_v<variant>.json in the output directory.  Usage: VARIANTS="-1 4" bash tools/traffic_ab.sh
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp

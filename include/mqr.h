@@ -447,6 +447,23 @@ int mqr_icp_pairs(mqr_cloudset* set, int n_pairs, const int32_t* src, const int3
 int mqr_information_pairs(mqr_cloudset* set, int n_pairs, const int32_t* src, const int32_t* tgt, double max_dist,
                           const double* T, double* info);
 
+/* ---- odometry information (make_fragments.py:106-240) -------------------------------------------
+ * o3d.t.pipelines.odometry.compute_odometry_information_matrix for n_pairs image pairs of one stack of
+ * N metric float32 depth frames (H x W each, host or device by depth_loc) in one launch.  K: the 3x3
+ * intrinsic matrix shared by the frames; T: n_pairs 4x4 transforms, source camera -> target camera
+ * (host float64).  info (host): n_pairs 6x6 float64 in the order (rx, ry, rz, tx, ty, tz); counts (host,
+ * may be NULL): the accepted pixels of each pair.  Float64 rules and a fixed summation order (DESIGN
+ * "odometry information rules"): a repeated call, and a pair alone or inside a batch, give identical
+ * bits.  The work runs on the calling thread's caller stream (mqr_set_stream) and the call returns with
+ * the host outputs filled.  n_pairs == 0 is a no-op; an index outside [0, N), a non-finite K or T or
+ * a non-positive N, H or W is status 2 before anything is launched.  The library keeps its device
+ * scratch (pairs, partial sums, results and, for MQR_HOST frames, a copy of the frame stack) per device
+ * for the life of the process, grow-only; there is no entry that releases it. */
+int mqr_odometry_information_pairs(int device, const float* depths, int depth_loc, int N, int H, int W,
+                                   const double* K, int n_pairs, const int32_t* src, const int32_t* tgt,
+                                   const double* T, double dist_threshold, double depth_scale, double depth_max,
+                                   double* info, int64_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,14 +30,15 @@
 #include <vector>
 
 #include "mqr_common.hpp"
+#include "pair_reduce.hpp"
 
 namespace mqr {
 namespace reg {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
+using pairsum::kInfoSums;  // count, 21 unique entries of sum G^T G
+using pairsum::kThreads;
+using pairsum::kWaves;
 constexpr int kIcpSums = 17;   // count, sum q (3), sum t (3), sum q t^T (9), sum d^2
-constexpr int kInfoSums = 22;  // count, 21 unique entries of sum G^T G
 constexpr double kCellLimit = 1048575.0;  // |cell index| < 2^20 per axis (pack_key)
 
 struct PairDesc {
@@ -186,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void k_corr(const PairDesc* __restrict__ 
             const double tx = (double)d.tpts[3 * (int64_t)j], ty = (double)d.tpts[3 * (int64_t)j + 1],
                          tz = (double)d.tpts[3 * (int64_t)j + 2];
             acc[0] = 1.0;
-            if (MODE == 0) {
+            if constexpr (MODE == 0) {
                 acc[1] = qx, acc[2] = qy, acc[3] = qz;
                 acc[4] = tx, acc[5] = ty, acc[6] = tz;
                 acc[7] = qx * tx, acc[8] = qx * ty, acc[9] = qx * tz;
@@ -194,31 +195,11 @@ __global__ __launch_bounds__(kThreads) void k_corr(const PairDesc* __restrict__ 
                 acc[13] = qz * tx, acc[14] = qz * ty, acc[15] = qz * tz;
                 acc[16] = d2;
             } else {
-                // G = [[0, z, -y, 1, 0, 0], [-z, 0, x, 0, 1, 0], [y, -x, 0, 0, 0, 1]]; upper triangle of
-                // G^T G row by row
-                acc[1] = tz * tz + ty * ty, acc[2] = -(tx * ty), acc[3] = -(tx * tz);
-                acc[4] = 0.0, acc[5] = -tz, acc[6] = ty;
-                acc[7] = tz * tz + tx * tx, acc[8] = -(ty * tz), acc[9] = tz, acc[10] = 0.0, acc[11] = -tx;
-                acc[12] = ty * ty + tx * tx, acc[13] = -ty, acc[14] = tx, acc[15] = 0.0;
-                acc[16] = 1.0, acc[17] = 0.0, acc[18] = 0.0;
-                acc[19] = 1.0, acc[20] = 0.0;
-                acc[21] = 1.0;
+                pairsum::info_sums(1.0, tx, ty, tz, tx * tx, ty * ty, tz * tz, tx * ty, tx * tz, ty * tz, acc);
             }
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-        double v = acc[j];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) sh[wave][j] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < NS) {
-        const int j = threadIdx.x;
-        slabs[((int64_t)d.slab_off + blockIdx.x) * NS + j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
-    }
+    pairsum::block_sums_to_slab<NS>(acc, sh, slabs + ((int64_t)d.slab_off + blockIdx.x) * NS);
 }
 
 // largest eigenvector of the symmetric 4x4 N (cyclic Jacobi), as a unit quaternion (w, x, y, z)
@@ -349,16 +330,7 @@ __global__ __launch_bounds__(64) void k_finalize_info(const PairDesc* __restrict
     __shared__ double S[kInfoSums];
     const int pair = blockIdx.x;
     const PairDesc d = pd[pair];
-    if (threadIdx.x < kInfoSums) {
-        double v = 0.0;
-        for (int b = 0; b < d.nblk; ++b) v += slabs[((int64_t)d.slab_off + b) * kInfoSums + threadIdx.x];
-        S[threadIdx.x] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x >= 36) return;
-    const int a = threadIdx.x / 6, b = threadIdx.x % 6;
-    const int r = a < b ? a : b, c = a < b ? b : a;
-    info[36 * (int64_t)pair + threadIdx.x] = S[1 + r * 6 - r * (r - 1) / 2 + (c - r)];
+    pairsum::info_from_slabs(slabs, d.slab_off, d.nblk, S, info + 36 * (int64_t)pair);
 }
 
 // ------------------------------------------------------------------ host side

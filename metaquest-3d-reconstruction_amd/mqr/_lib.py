@@ -151,6 +151,10 @@ SIGNATURES = {
     "mqr_icp_pairs": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_int, _f64p, _f64p, _i32p, _f64p,
                                      _f64p, _f64p, _f64p, _f64p, _f64p, _i32p]),
     "mqr_information_pairs": (ctypes.c_int, [_vp, ctypes.c_int, _i32p, _i32p, ctypes.c_double, _f64p, _f64p]),
+    "mqr_odometry_information_pairs": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int, _f64p, ctypes.c_int, _i32p, _i32p, _f64p,
+                                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p,
+                                                      _i64p]),
 }
 
 _lib = None
@@ -248,6 +252,7 @@ ORDERED = frozenset({
     "mqr_color_map", "mqr_scene_add_triangles", "mqr_scene_cast_pinhole", "mqr_scene_cast_rays",
     "mqr_mesh_filter_components", "mqr_memcpy",
     "mqr_cloudset_create", "mqr_cloudset_voxel_down", "mqr_evaluate_pairs", "mqr_icp_pairs", "mqr_information_pairs",
+    "mqr_odometry_information_pairs",
 })
 _tls = threading.local()
 

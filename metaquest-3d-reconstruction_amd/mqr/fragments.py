@@ -7,6 +7,8 @@
     compute_pcd_pair_edge(clouds, source_node, target_node, config, uncertain)            :122-193
     build_pose_graph_for_scene(fragment_clouds_by_side, config)                           :196-271
         the pose-graph edges of every fragment pair, registered on the GPU (mqr.registration)
+    refine_fragment_poses(depth_data_io, fragment_dataset_map, config, workers)           :274-321
+        integrate, register, optimise the scene graph (mqr.posegraph), move the fragments
 
 Each fragment (``fragment_size`` = 100 frames, pipeline_config.yml:38) is integrated into a FRESH
 volume (``vbg_opt=None``) and its point cloud extracted with the default weight threshold 3.0; a
@@ -27,6 +29,7 @@ from typing import List, Optional
 import numpy as np
 
 from .models import Side
+from .posegraph import PoseGraph, PoseGraphEdge, PoseGraphNode  # noqa: F401  (re-exported)
 
 
 @dataclass
@@ -149,64 +152,15 @@ def integrate_fragment_point_clouds(depth_data_io, fragment_dataset_map, config:
 
 
 def fragment_datasets(dataset, fragment_size: int = 100):
-    """Consecutive fragment_size-frame slices of a dataset (make_fragments.py's fragment layout;
-    its odometry and loop closure are out of scope)."""
+    """Consecutive fragment_size-frame slices of a dataset (make_fragments.py's fragment layout; the
+    fragments' own pose graphs are mqr.make_fragments)."""
     n = len(dataset)
     return [dataset[list(range(a, min(n, a + fragment_size)))] for a in range(0, n, fragment_size)]
 
 
 # ---- pose graph of the fragments (refine_fragment_poses.py:122-271) --------------------------------
-# Plain containers with Open3D's attribute names; to_legacy() gives the real
-# o3d.pipelines.registration objects when open3d imports (as mqr.geometry does).  The optimisation of
-# the graph (o3d.pipelines.registration.global_optimization) is not part of this package.
-@dataclass
-class PoseGraphNode:
-    pose: np.ndarray = field(default_factory=lambda: np.eye(4))
-
-    def to_legacy(self):
-        from .geometry import _try_open3d
-        o3d = _try_open3d()
-        return self if o3d is None else o3d.pipelines.registration.PoseGraphNode(pose=np.asarray(self.pose))
-
-
-@dataclass
-class PoseGraphEdge:
-    source_node_id: int = -1
-    target_node_id: int = -1
-    transformation: np.ndarray = field(default_factory=lambda: np.eye(4))
-    information: np.ndarray = field(default_factory=lambda: np.eye(6))
-    uncertain: bool = False
-    confidence: float = 1.0
-
-    def to_legacy(self):
-        from .geometry import _try_open3d
-        o3d = _try_open3d()
-        if o3d is None:
-            return self
-        return o3d.pipelines.registration.PoseGraphEdge(
-            source_node_id=self.source_node_id, target_node_id=self.target_node_id,
-            transformation=np.asarray(self.transformation), information=np.asarray(self.information),
-            uncertain=self.uncertain, confidence=self.confidence)
-
-
-@dataclass
-class PoseGraph:
-    nodes: List[PoseGraphNode] = field(default_factory=list)
-    edges: List[PoseGraphEdge] = field(default_factory=list)
-
-    def to_legacy(self):
-        from .geometry import _try_open3d
-        o3d = _try_open3d()
-        if o3d is None:
-            return self
-        g = o3d.pipelines.registration.PoseGraph()
-        for n in self.nodes:
-            g.nodes.append(n.to_legacy())
-        for e in self.edges:
-            g.edges.append(e.to_legacy())
-        return g
-
-
+# The containers (Open3D's attribute names) live in mqr.posegraph with the optimiser; they are imported
+# above so that ``from mqr.fragments import PoseGraph`` keeps working.
 def _pre_filter_rejects(result, config) -> bool:
     return (result.fitness < config.pre_filter_fitness_threshold
             or result.inlier_rmse > config.pre_filter_inlier_rmse_threshold)
@@ -295,3 +249,43 @@ def build_pose_graph_for_scene(fragment_clouds_by_side, config: FragmentPoseRefi
     print(f"[Info] Valid edges: {len(valid_edges)} / {len(edges)}")
     graph.edges.extend(valid_edges)
     return graph, node_side_index_list
+
+
+def refine_fragment_poses(depth_data_io, fragment_dataset_map, config: FragmentPoseRefinementConfig,
+                          workers: Optional[int] = None):
+    """refine_fragment_poses.py:274-321 in memory: integrate every fragment, register every pair of the
+    fragments that gave a cloud (build_pose_graph_for_scene), optimise the scene graph with node 0 fixed
+    and move each fragment by its node's pose.  Changes the fragments' transforms in place and returns
+    (pose_graph, node_side_index_list).
+
+    Fragments that fail to integrate are dropped the way the reference's fragment_counts drops them: the
+    clouds of a side are numbered in order, so node (side, k) stands for the side's k-th SAVED cloud and
+    moves ``fragment_dataset_map[side][k]`` (after a failure these differ, as in the reference).  Without
+    use_multi_threading the clouds stay in HBM between integration and registration."""
+    from .geometry import PointCloud
+    from .o3d_utils import convert_pose_graph_to_transforms
+    from .posegraph import GlobalOptimizationConvergenceCriteria, GlobalOptimizationOption, global_optimization
+    in_process = not config.use_multi_threading
+    results = integrate_fragment_point_clouds(depth_data_io, fragment_dataset_map, config, workers=workers,
+                                              keep_on_device=in_process)
+    valid = [r for r in results if r is not None]
+    failed = len(results) - len(valid)
+    if failed > 0:
+        print(f"[Warning] {failed} out of {len(results)} fragment point clouds failed to integrate or were empty.")
+    if not valid:
+        raise Exception("Failed to integrate fragment point clouds: all fragments produced empty or invalid point clouds.")
+    clouds_by_side = {}
+    for r in valid:
+        cloud = r[1] if in_process else PointCloud(r[1], r[2])
+        clouds_by_side.setdefault(r[0], []).append(cloud)
+    print(f"[Info] Successfully integrated {len(valid)} fragment point clouds.")
+    pose_graph, node_side_index_list = build_pose_graph_for_scene(clouds_by_side, config)
+    del clouds_by_side, valid, results
+    option = GlobalOptimizationOption(max_correspondence_distance=config.dist_threshold,
+                                      edge_prune_threshold=config.edge_prune_threshold, reference_node=0)
+    global_optimization(pose_graph, option, GlobalOptimizationConvergenceCriteria())
+    moves = convert_pose_graph_to_transforms(pose_graph)
+    for (side, k), shift, turn in zip(node_side_index_list, moves.positions, moves.rotations):
+        frag = fragment_dataset_map[side][k]
+        frag.transforms = frag.transforms.apply_world_transform(delta_position=shift, delta_rotation=turn)
+    return pose_graph, node_side_index_list

@@ -107,6 +107,13 @@ class Transforms:
             rot = rot @ _camera_basis(target_coordinate_system)
         return Transforms(target_coordinate_system, positions, Rotation.from_matrix(rot).as_quat())
 
+    def apply_world_transform(self, delta_position: np.ndarray, delta_rotation: np.ndarray) -> "Transforms":
+        """Every pose moved by one world transform (transforms.py:242-258): delta_rotation (x, y, z, w)
+        rotates positions and orientations, then delta_position is added."""
+        delta = Rotation.from_quat(delta_rotation)
+        return Transforms(self.coordinate_system, delta.apply(self.positions) + delta_position,
+                          (delta * Rotation.from_quat(self.rotations)).as_quat())
+
     def to_dict(self) -> dict:
         return {"coordinate_system": self.coordinate_system, "positions": self.positions,
                 "rotations": self.rotations}
@@ -182,6 +189,33 @@ class CameraDataset:
 
     def split(self, fragment_size: int):
         return [self[i:i + fragment_size] for i in range(0, len(self), fragment_size)]
+
+    @classmethod
+    def merge(cls, datasets):
+        """The frames of several datasets of one capture as one dataset, in the order given (the
+        reference's ``merge``, camera_dataset.py:167-192): every per-frame field is joined along the frame
+        axis; a field that is not per-frame (the directory, the coordinate system) has to be the same in
+        all of them.  ValueError when the datasets do not fit together."""
+        datasets = list(datasets)
+        if not datasets:
+            raise ValueError("merge needs at least one dataset")
+        fields = [ds.to_dict() for ds in datasets]
+        first = fields[0]
+        joined = {}
+        for name, head in first.items():
+            column = [f[name] for f in fields]
+            per_frame = isinstance(head, np.ndarray) and head.ndim >= 1
+            for other in column[1:]:
+                if type(other) is not type(head):
+                    raise ValueError(f"merge: field '{name}' is a {type(head).__name__} in one dataset and a "
+                                     f"{type(other).__name__} in another")
+                if per_frame and other.shape[1:] != head.shape[1:]:
+                    raise ValueError(f"merge: field '{name}' has per-frame shape {head.shape[1:]} in one dataset "
+                                     f"and {other.shape[1:]} in another")
+                if not per_frame and not np.all(other == head):
+                    raise ValueError(f"merge: field '{name}' differs between the datasets ({head!r} and {other!r})")
+            joined[name] = np.concatenate(column, axis=0) if per_frame else head
+        return cls.from_dict(joined)
 
     def save(self, path: Path):
         path = Path(path)

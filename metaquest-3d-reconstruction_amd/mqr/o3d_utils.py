@@ -1,6 +1,8 @@
 """Drop-in for the reference's ``processing/reconstruction/utils/o3d_utils.py`` fusion entry points.
 
     compute_o3d_intrinsic_matrices(dataset)          o3d_utils.py:14-19
+    convert_transforms_to_pose_graph(transforms)     o3d_utils.py:22-35
+    convert_pose_graph_to_transforms(pose_graph)     o3d_utils.py:99-106
     load_depth_map(...)                              o3d_utils.py:109-150
     integrate(dataset, depth_data_io, side, ...)     o3d_utils.py:153-238
 
@@ -80,6 +82,22 @@ def compute_o3d_intrinsic_matrices(dataset) -> np.ndarray:
     k = dataset.get_intrinsic_matrices()
     k[:, 0, 2] = widths - k[:, 0, 2]
     return k
+
+
+def convert_transforms_to_pose_graph(transforms):
+    """One node per pose, holding its camera->world matrix (o3d_utils.py:22-35); no edges."""
+    from .posegraph import PoseGraph, PoseGraphNode
+    return PoseGraph(nodes=[PoseGraphNode(pose=m) for m in transforms.extrinsics_cw])
+
+
+def convert_pose_graph_to_transforms(pose_graph):
+    """The nodes' poses as OPEN3D Transforms (o3d_utils.py:99-106)."""
+    from scipy.spatial.transform import Rotation
+    from .models import CoordinateSystem, Transforms
+    nodes = pose_graph.nodes
+    matrices = np.stack([np.asarray(n.pose) for n in nodes]) if len(nodes) else np.zeros((0, 4, 4))
+    quats = Rotation.from_matrix(matrices[:, :3, :3]).as_quat() if len(nodes) else np.zeros((0, 4))
+    return Transforms(CoordinateSystem.OPEN3D, matrices[:, :3, 3], quats)
 
 
 def _masked_depth(depth_data_io, side, index, dataset, use_confidence_filtered_depth, confidence_threshold,

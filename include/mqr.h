@@ -377,7 +377,7 @@ int mqr_color_vertices(int device, const float* vertices, int64_t nv, int vertic
                        double max_depth, double visibility_threshold, int margin, float* colors_out,
                        int32_t* counts_out, int out_loc);
 /* mqr_color_map: the complete vertex colouring of run_rigid_optimizer with the keyframe poses as
- * given (optimize_color_pose.py:70-73; pose refinement OUT of scope): t_hit = raycast_in_color_view
+ * given (optimize_color_pose.py:70-73 at maximum_iteration = 0; the refinement: mqr_colormap_*): t_hit = raycast_in_color_view
  * depth (o3d_utils.py:324-341), RGBD depth truncated at depth_trunc (3.0), depth-discontinuity
  * masks (Sobel magnitude > disc_threshold 0.1, dilated by half_dilation 3), visibility, float64
  * colour means, and vertices no keyframe samples filled with the mean of their knn (3) nearest
@@ -463,6 +463,49 @@ int mqr_odometry_information_pairs(int device, const float* depths, int depth_lo
                                    const double* K, int n_pairs, const int32_t* src, const int32_t* tgt,
                                    const double* T, double dist_threshold, double depth_scale, double depth_max,
                                    double* info, int64_t* counts);
+
+/* ---- colour-map optimisation (optimize_color_pose.py:70-73) --------------------------------------
+ * o3d.pipelines.color_map.run_rigid_optimizer, device resident from start to finish (the
+ * rules, restated from Open3D 0.19 as recalled).  A handle holds the vertices, the keyframes' utility
+ * images (grey, d/dx, d/dy), the depth-boundary masks' outcome -- both visibility lists, computed once
+ * at the poses given to create -- and the current poses, all in HBM.
+ * create: arguments as mqr_color_map (vertices nv*3 float32 by vloc; images N*H*W*3 uint8 and t_hit
+ *   N*H*W float32 by iloc; K N*9, T_wc N*16 float64 host).  MQR_DEVICE vertices and images are used in
+ *   place and must stay valid and unchanged until destroy; t_hit is only read by create.  H, W >= 2,
+ *   margin >= 0, N <= 65535.  A non-finite K or T_wc is status 2 ("non-finite").  N == 0 or nv == 0
+ *   gives a handle that touches no device: every call on it succeeds and reports zeros.
+ * counts: the visibility pairs of each keyframe (N int64, host).
+ * set_poses / get_poses: N*16 float64 host, world -> camera.  The visibility lists stay as created.
+ * proxy: recomputes every vertex's proxy intensity at the current poses; proxy (nv float64, host) may
+ *   be NULL.
+ * systems: one evaluation at the current poses and proxies, no update: JTJ N*36 (symmetric), JTr N*6,
+ *   r2 N, count N (host).  Proxies older than the last set_poses are recomputed first.
+ * optimize: max_iteration iterations of (all systems, all pose updates, proxies) enqueued back to back;
+ *   residuals[it] = the sum of the keyframes' r2 and counts[it] = their terms in iteration it (host,
+ *   read once at the end).  max_iteration == 0 is a no-op.
+ * colors: the float64 mean colours over the visibility pairs at the current poses, then mqr_color_map's
+ *   fill of unsampled vertices from their knn (0..8) nearest sampled ones; colors nv*3 float32 and
+ *   counts nv int32 (may be NULL) by loc.  With the poses as created it is bit-identical to
+ *   mqr_color_map.
+ * Every sum has a fixed order (no float atomics): repeated runs are bit-identical.  A handle serves one
+ * thread at a time. */
+typedef struct mqr_colormap mqr_colormap;
+int mqr_colormap_create(int device, const float* vertices, int64_t nv, int vloc, const uint8_t* images,
+                        const float* t_hit, int iloc, int N, int H, int W, const double* K, const double* T_wc,
+                        double max_depth, double visibility_threshold, int margin, double disc_threshold,
+                        int half_dilation, double depth_trunc, mqr_colormap** out);
+int mqr_colormap_counts(mqr_colormap* h, int64_t* pairs_per_keyframe);
+int mqr_colormap_set_poses(mqr_colormap* h, const double* T_wc);
+int mqr_colormap_get_poses(mqr_colormap* h, double* T_wc);
+int mqr_colormap_proxy(mqr_colormap* h, double* proxy);
+int mqr_colormap_systems(mqr_colormap* h, double* JTJ, double* JTr, double* r2, int64_t* count);
+int mqr_colormap_optimize(mqr_colormap* h, int max_iteration, double* residuals, int64_t* counts);
+int mqr_colormap_colors(mqr_colormap* h, int knn, float* colors, int32_t* counts, int loc);
+/* Device time of the last optimize's launches (events on the handle's stream around the loop), ms. */
+int mqr_colormap_optimize_ms(mqr_colormap* h, float* ms);
+/* Hash of the colour-map optimiser's sources compiled into the library (for profile records). */
+int mqr_colormap_build_tag(char* buf, int n);
+int mqr_colormap_destroy(mqr_colormap* h);
 
 #ifdef __cplusplus
 }

@@ -15,7 +15,8 @@
 //   keyframe order.
 // mqr_color_vertices is that visibility-and-average primitive; mqr_color_map (below) is the complete
 // assignment -- RGBD depth truncation, depth-discontinuity masks, float64 averages and the
-// k-nearest-neighbour fill of vertices no keyframe sees.  The pose optimisation stays OUT of scope.
+// k-nearest-neighbour fill of vertices no keyframe sees.  The pose optimisation is colormap.hip's; it shares
+// the masks and the fill with this file through color_shared.hpp.
 //
 // One thread per vertex, keyframe loop in registers; the keyframe parameters sit in constant-
 // cached global memory.  Colour images are RGB uint8 [N][H][W][3], depth float32 [N][H][W].
@@ -28,13 +29,9 @@
 
 #include "mqr_common.hpp"
 #include "device_block.hpp"
+#include "color_shared.hpp"
 
 namespace mqr {
-
-struct ColorCam {
-    double E[12];  // world -> camera, rows 0..2 of T_wc
-    double fx, fy, cx, cy;
-};
 
 __global__ __launch_bounds__(256) void k_color_vertices(const float* __restrict__ V, int64_t nv,
                                                         const uint8_t* __restrict__ images,
@@ -77,8 +74,8 @@ __global__ __launch_bounds__(256) void k_color_vertices(const float* __restrict_
 }
 
 // ================================================================== complete colour map (mqr_color_map)
-// run_rigid_optimizer's vertex colours with the keyframe poses as given (the pose refinement stays
-// OUT of scope; = maximum_iteration 0), upstream ColorMapUtils / Image.cpp as recalled -- VERIFY:
+// run_rigid_optimizer's vertex colours with the keyframe poses as given (= maximum_iteration 0; the pose
+// refinement is colormap.hip), upstream ColorMapUtils / Image.cpp as recalled -- VERIFY:
 //   RGBD depth d = t_hit / 1.0, d >= depth_trunc (3.0, create_from_color_and_depth's default) -> 0;
 //   depth-boundary mask: Sobel dx = (Sobel31 along x, then Sobel32 along y), dy = (Sobel32, Sobel31),
 //     every pass a float32 image of double sums of float products over the clamped 3-tap window;
@@ -512,6 +509,122 @@ __global__ void k_cm_flags(const int32_t* __restrict__ counts, int64_t nv, uint8
     unseen[i] = counts[i] == 0;
 }
 
+void cm_enqueue_masks(hipStream_t s, const float* t_hit, int64_t NHW, int H, int W, float depth_trunc,
+                      double disc_threshold, int half_dilation, float* hx, float* hy, uint8_t* m0, uint8_t* mask) {
+    if (NHW <= 0) return;
+    const unsigned gi = (unsigned)((NHW + 255) / 256);
+    hipLaunchKernelGGL(k_cm_filter_h, dim3(gi), dim3(256), 0, s, t_hit, NHW, H, W, depth_trunc, hx, hy);
+    hipLaunchKernelGGL(k_cm_filter_v, dim3(gi), dim3(256), 0, s, hx, hy, NHW, H, W, disc_threshold, m0);
+    hipLaunchKernelGGL(k_cm_dilate, dim3(gi), dim3(256), 0, s, m0, NHW, H, W, half_dilation, mask);
+}
+
+int cm_finish_colors(int device, hipStream_t s, const float* dV, int64_t nv, const double* avg, const int32_t* cnt,
+                     int knn, float* dO, const char* who) {
+    int rc = 0;
+    auto fail = [&](const char* msg) {
+        set_error(std::string(who) + ": " + msg);
+        rc = 1;
+    };
+    size_t tb_sel = 0;
+    hipcub::CountingInputIterator<int32_t> it(0);
+    if (hipcub::DeviceSelect::Flagged(nullptr, tb_sel, it, (const uint8_t*)nullptr, (int32_t*)nullptr,
+                                      (int64_t*)nullptr, (int)nv, s) != hipSuccess) {
+        fail("select sizing failed");
+        return rc;
+    }
+    // device staging from the device-block cache (device_block.hpp): the flags and index lists in one block,
+    // the knn pass's (sized once the seen vertices are counted) in a second; both returned after the final
+    // synchronisation
+    CachedBlock blk(device, (1 + 1 + 8) * (size_t)nv + 16 + tb_sel + 8 * 256);
+    std::unique_ptr<CachedBlock> blk_knn;
+    CachedBlock* cur = &blk;
+    auto alloc = [&](size_t bytes) -> void* { return cur->take(std::max<size_t>(bytes, 16)); };
+    uint8_t* fseen = static_cast<uint8_t*>(alloc(nv));
+    uint8_t* funseen = static_cast<uint8_t*>(alloc(nv));
+    int32_t* ids = static_cast<int32_t*>(alloc(sizeof(int32_t) * 2 * nv));  // seen, then unseen
+    int64_t* nsel = static_cast<int64_t*>(alloc(2 * sizeof(int64_t)));
+    void* tmp = alloc(tb_sel);
+    if (!fseen || !funseen || !ids || !nsel || !tmp) fail("device allocation or upload failed");
+    int64_t nseen = 0, nunseen = 0;
+    if (!rc) {
+        const unsigned gv = (unsigned)((nv + 255) / 256);
+        hipLaunchKernelGGL(k_cm_flags, dim3(gv), dim3(256), 0, s, cnt, nv, fseen, funseen);
+        size_t tb = tb_sel;
+        if (hipcub::DeviceSelect::Flagged(tmp, tb, it, fseen, ids, nsel, (int)nv, s) != hipSuccess ||
+            hipcub::DeviceSelect::Flagged(tmp, tb, it, funseen, ids + nv, nsel + 1, (int)nv, s) != hipSuccess)
+            fail("select failed");
+        int64_t h[2] = {0, 0};
+        if (!rc && (hipMemcpyAsync(h, nsel, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                    hipStreamSynchronize(s) != hipSuccess))
+            fail("visibility pass failed");
+        nseen = h[0];
+        nunseen = h[1];
+        if (!rc && hipMemsetAsync(dO, 0, sizeof(float) * 3 * nv, s) != hipSuccess) fail("memset failed");
+        if (!rc && nseen > 0)
+            hipLaunchKernelGGL(k_cm_out_seen, dim3(gv), dim3(256), 0, s, avg, cnt, nv, dO);
+        if (!rc && knn > 0 && nseen > 0 && nunseen > 0) {
+            const int64_t nb = (nseen + kBucket - 1) / kBucket;
+            int64_t P = 1;
+            while (P < nb) P <<= 1;
+            size_t tbs = 0;
+            if (hipcub::DeviceRadixSort::SortPairs(nullptr, tbs, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                   (const int32_t*)nullptr, (int32_t*)nullptr, (int)nseen, 0, 63, s) !=
+                hipSuccess)
+                fail("knn allocation failed");
+            blk_knn.reset(new CachedBlock(device, 24 + 16 * (size_t)nseen + 4 * (size_t)nseen + 64 * (size_t)P +
+                                                      16 * (size_t)nseen + tbs + 8 * 256));
+            cur = blk_knn.get();
+            uint32_t* bb = static_cast<uint32_t*>(alloc(6 * sizeof(uint32_t)));
+            uint64_t* keys = static_cast<uint64_t*>(alloc(sizeof(uint64_t) * 2 * nseen));
+            int32_t* sorted = static_cast<int32_t*>(alloc(sizeof(int32_t) * nseen));
+            float4* blo = static_cast<float4*>(alloc(sizeof(float4) * 2 * P));
+            float4* bhi = static_cast<float4*>(alloc(sizeof(float4) * 2 * P));
+            float4* pts = static_cast<float4*>(alloc(sizeof(float4) * nseen));
+            if (!rc && (!bb || !keys || !sorted || !blo || !bhi || !pts)) fail("knn allocation failed");
+            void* tmps = rc ? nullptr : alloc(tbs);
+            if (!rc && !tmps) fail("knn allocation failed");
+            if (!rc) {
+                const uint32_t init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
+                const unsigned gs = (unsigned)((nseen + 255) / 256);
+                if (hipMemcpyAsync(bb, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) fail("copy");
+                hipLaunchKernelGGL(k_cm_bounds, dim3(std::min(gs, 4096u)), dim3(256), 0, s, dV, ids, nseen, bb);
+                hipLaunchKernelGGL(k_cm_morton, dim3(gs), dim3(256), 0, s, dV, ids, nseen, bb, keys);
+                if (hipcub::DeviceRadixSort::SortPairs(tmps, tbs, keys, keys + nseen, ids, sorted, (int)nseen, 0, 63, s) !=
+                    hipSuccess)
+                    fail("sort failed");
+                hipLaunchKernelGGL(k_cm_leaf_boxes, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, dV, sorted, nseen,
+                                   P, blo, bhi, pts);
+                for (int64_t first = P / 2; first >= 1; first /= 2)
+                    hipLaunchKernelGGL(k_cm_level, dim3((unsigned)((first + 255) / 256)), dim3(256), 0, s, first, first,
+                                       blo, bhi);
+                const dim3 gq((unsigned)((nunseen + 255) / 256));
+                int depth = 0;  // levels below the root of the P-leaf tree
+                while ((int64_t{1} << depth) < P) ++depth;
+                const bool wave = MQR_KNN_WAVE && depth + 2 <= 64;  // (the wave stack holds 64 entries)
+                const size_t lds = wave ? sizeof(int32_t) * 4 * 64 : sizeof(int32_t) * 256 * (size_t)(depth + 2);
+                auto fill = [&](auto kern) {
+                    hipLaunchKernelGGL(kern, gq, dim3(256), lds, s, dV, ids + nv, nunseen, pts, nseen, P, blo, bhi,
+                                       avg, dO);
+                };
+                switch (knn) {  // knn in [1, 8] (checked on entry)
+                    case 1: wave ? fill(k_cm_knn_fill_wave<1>) : fill(k_cm_knn_fill<1>); break;
+                    case 2: wave ? fill(k_cm_knn_fill_wave<2>) : fill(k_cm_knn_fill<2>); break;
+                    case 3: wave ? fill(k_cm_knn_fill_wave<3>) : fill(k_cm_knn_fill<3>); break;
+                    case 4: wave ? fill(k_cm_knn_fill_wave<4>) : fill(k_cm_knn_fill<4>); break;
+                    case 5: wave ? fill(k_cm_knn_fill_wave<5>) : fill(k_cm_knn_fill<5>); break;
+                    case 6: wave ? fill(k_cm_knn_fill_wave<6>) : fill(k_cm_knn_fill<6>); break;
+                    case 7: wave ? fill(k_cm_knn_fill_wave<7>) : fill(k_cm_knn_fill<7>); break;
+                    default: wave ? fill(k_cm_knn_fill_wave<8>) : fill(k_cm_knn_fill<8>); break;
+                }
+            }
+        }
+        if (!rc && hipGetLastError() != hipSuccess) fail("kernel launch failed");
+    }
+    // the staging blocks go back to the cache at scope exit: everything queued on them has to be done
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) fail("kernel failed");
+    return rc;
+}
+
 }  // namespace mqr
 
 using namespace mqr;
@@ -612,25 +725,12 @@ int mqr_color_map(int device, const float* vertices, int64_t nv, int vloc, const
         return 2;
     }
     // device staging from the device-block cache (device_block.hpp): the visibility pass's arrays in one
-    // block, the knn pass's (sized once the seen vertices are counted) in a second; both returned after
-    // the final synchronisation
+    // block (the fill's are cm_finish_colors' own), returned after the final synchronisation
     const int64_t HW0 = (int64_t)H * W, NHW0 = HW0 * N;
-    size_t tb_sel = 0;
-    {
-        hipcub::CountingInputIterator<int32_t> it0(0);
-        if (hipcub::DeviceSelect::Flagged(nullptr, tb_sel, it0, (const uint8_t*)nullptr, (int32_t*)nullptr,
-                                          (int64_t*)nullptr, (int)nv, s) != hipSuccess) {
-            (void)hipStreamDestroy(s);
-            set_error("mqr_color_map: select sizing failed");
-            return 1;
-        }
-    }
     const bool hv = vloc != MQR_DEVICE, hi = img_loc != MQR_DEVICE;
     CachedBlock blk(device, (hv ? 12 * (size_t)nv : 0) + (hi ? 7 * (size_t)NHW0 : 0) + sizeof(ColorCam) * std::max(N, 1) +
-                                10 * (size_t)NHW0 + (24 + 4 + 12 + 1 + 1 + 8) * (size_t)nv + 16 + tb_sel + 16 * 256);
-    std::unique_ptr<CachedBlock> blk_knn;
-    CachedBlock* cur = &blk;
-    auto alloc = [&](size_t bytes) -> void* { return cur->take(std::max<size_t>(bytes, 16)); };
+                                10 * (size_t)NHW0 + (24 + 4 + 12) * (size_t)nv + 16 * 256);
+    auto alloc = [&](size_t bytes) -> void* { return blk.take(std::max<size_t>(bytes, 16)); };
     auto dev = [&](const void* h, size_t bytes, bool host) -> const void* {
         if (!host) return h;
         void* p = alloc(bytes);
@@ -654,97 +754,16 @@ int mqr_color_map(int device, const float* vertices, int64_t nv, int vloc, const
     double* avg = static_cast<double*>(alloc(sizeof(double) * 3 * nv));
     int32_t* cnt = static_cast<int32_t*>(alloc(sizeof(int32_t) * nv));
     float* dO = out_loc == MQR_DEVICE ? colors_out : static_cast<float*>(alloc(sizeof(float) * 3 * nv));
-    uint8_t* fseen = static_cast<uint8_t*>(alloc(nv));
-    uint8_t* funseen = static_cast<uint8_t*>(alloc(nv));
-    int32_t* ids = static_cast<int32_t*>(alloc(sizeof(int32_t) * 2 * nv));  // seen, then unseen
-    int64_t* nsel = static_cast<int64_t*>(alloc(2 * sizeof(int64_t)));
-    if (!dV || !dI || !dT || !dC || !hx || !hy || !m0 || !mask || !avg || !cnt || !dO || !fseen || !funseen || !ids ||
-        !nsel) {
+    if (!dV || !dI || !dT || !dC || !hx || !hy || !m0 || !mask || !avg || !cnt || !dO) {
         fail("mqr_color_map: device allocation or upload failed");
     }
-    int64_t nseen = 0, nunseen = 0;
     if (!rc) {
-        const unsigned gi = (unsigned)((NHW + 255) / 256), gv = (unsigned)((nv + 255) / 256);
-        if (NHW > 0) {
-            hipLaunchKernelGGL(k_cm_filter_h, dim3(gi), dim3(256), 0, s, dT, NHW, H, W, (float)depth_trunc, hx, hy);
-            hipLaunchKernelGGL(k_cm_filter_v, dim3(gi), dim3(256), 0, s, hx, hy, NHW, H, W, disc_threshold, m0);
-            hipLaunchKernelGGL(k_cm_dilate, dim3(gi), dim3(256), 0, s, m0, NHW, H, W, half_dilation, mask);
-        }
+        const unsigned gv = (unsigned)((nv + 255) / 256);
+        cm_enqueue_masks(s, dT, NHW, H, W, (float)depth_trunc, disc_threshold, half_dilation, hx, hy, m0, mask);
         hipLaunchKernelGGL(k_cm_vertices, dim3(gv), dim3(256), 0, s, dV, nv, dI, dT, mask, dC, N, H, W, max_depth,
                            visibility_threshold, margin, (float)depth_trunc, avg, cnt);
-        hipLaunchKernelGGL(k_cm_flags, dim3(gv), dim3(256), 0, s, cnt, nv, fseen, funseen);
-        size_t tb = tb_sel;
-        hipcub::CountingInputIterator<int32_t> it(0);
-        void* tmp = rc ? nullptr : alloc(tb);
-        if (!rc && (!tmp || hipcub::DeviceSelect::Flagged(tmp, tb, it, fseen, ids, nsel, (int)nv, s) != hipSuccess ||
-                    hipcub::DeviceSelect::Flagged(tmp, tb, it, funseen, ids + nv, nsel + 1, (int)nv, s) != hipSuccess))
-            fail("mqr_color_map: select failed");
-        int64_t h[2] = {0, 0};
-        if (!rc && (hipMemcpyAsync(h, nsel, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                    hipStreamSynchronize(s) != hipSuccess))
-            fail("mqr_color_map: visibility pass failed");
-        nseen = h[0];
-        nunseen = h[1];
-        if (!rc && hipMemsetAsync(dO, 0, sizeof(float) * 3 * nv, s) != hipSuccess) fail("mqr_color_map: memset failed");
-        if (!rc && nseen > 0)
-            hipLaunchKernelGGL(k_cm_out_seen, dim3(gv), dim3(256), 0, s, avg, cnt, nv, dO);
-        if (!rc && knn > 0 && nseen > 0 && nunseen > 0) {
-            const int64_t nb = (nseen + kBucket - 1) / kBucket;
-            int64_t P = 1;
-            while (P < nb) P <<= 1;
-            size_t tbs = 0;
-            if (hipcub::DeviceRadixSort::SortPairs(nullptr, tbs, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                   (const int32_t*)nullptr, (int32_t*)nullptr, (int)nseen, 0, 63, s) !=
-                hipSuccess)
-                fail("mqr_color_map: knn allocation failed");
-            blk_knn.reset(new CachedBlock(device, 24 + 16 * (size_t)nseen + 4 * (size_t)nseen + 64 * (size_t)P +
-                                                      16 * (size_t)nseen + tbs + 8 * 256));
-            cur = blk_knn.get();
-            uint32_t* bb = static_cast<uint32_t*>(alloc(6 * sizeof(uint32_t)));
-            uint64_t* keys = static_cast<uint64_t*>(alloc(sizeof(uint64_t) * 2 * nseen));
-            int32_t* sorted = static_cast<int32_t*>(alloc(sizeof(int32_t) * nseen));
-            float4* blo = static_cast<float4*>(alloc(sizeof(float4) * 2 * P));
-            float4* bhi = static_cast<float4*>(alloc(sizeof(float4) * 2 * P));
-            float4* pts = static_cast<float4*>(alloc(sizeof(float4) * nseen));
-            if (!rc && (!bb || !keys || !sorted || !blo || !bhi || !pts)) fail("mqr_color_map: knn allocation failed");
-            void* tmps = rc ? nullptr : alloc(tbs);
-            if (!rc && !tmps) fail("mqr_color_map: knn allocation failed");
-            if (!rc) {
-                const uint32_t init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
-                const unsigned gs = (unsigned)((nseen + 255) / 256);
-                if (hipMemcpyAsync(bb, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) fail("mqr_color_map: copy");
-                hipLaunchKernelGGL(k_cm_bounds, dim3(std::min(gs, 4096u)), dim3(256), 0, s, dV, ids, nseen, bb);
-                hipLaunchKernelGGL(k_cm_morton, dim3(gs), dim3(256), 0, s, dV, ids, nseen, bb, keys);
-                if (hipcub::DeviceRadixSort::SortPairs(tmps, tbs, keys, keys + nseen, ids, sorted, (int)nseen, 0, 63, s) !=
-                    hipSuccess)
-                    fail("mqr_color_map: sort failed");
-                hipLaunchKernelGGL(k_cm_leaf_boxes, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, dV, sorted, nseen,
-                                   P, blo, bhi, pts);
-                for (int64_t first = P / 2; first >= 1; first /= 2)
-                    hipLaunchKernelGGL(k_cm_level, dim3((unsigned)((first + 255) / 256)), dim3(256), 0, s, first, first,
-                                       blo, bhi);
-                const dim3 gq((unsigned)((nunseen + 255) / 256));
-                int depth = 0;  // levels below the root of the P-leaf tree
-                while ((int64_t{1} << depth) < P) ++depth;
-                const bool wave = MQR_KNN_WAVE && depth + 2 <= 64;  // (the wave stack holds 64 entries)
-                const size_t lds = wave ? sizeof(int32_t) * 4 * 64 : sizeof(int32_t) * 256 * (size_t)(depth + 2);
-                auto fill = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, gq, dim3(256), lds, s, dV, ids + nv, nunseen, pts, nseen, P, blo, bhi,
-                                       avg, dO);
-                };
-                switch (knn) {  // knn in [1, 8] (checked on entry)
-                    case 1: wave ? fill(k_cm_knn_fill_wave<1>) : fill(k_cm_knn_fill<1>); break;
-                    case 2: wave ? fill(k_cm_knn_fill_wave<2>) : fill(k_cm_knn_fill<2>); break;
-                    case 3: wave ? fill(k_cm_knn_fill_wave<3>) : fill(k_cm_knn_fill<3>); break;
-                    case 4: wave ? fill(k_cm_knn_fill_wave<4>) : fill(k_cm_knn_fill<4>); break;
-                    case 5: wave ? fill(k_cm_knn_fill_wave<5>) : fill(k_cm_knn_fill<5>); break;
-                    case 6: wave ? fill(k_cm_knn_fill_wave<6>) : fill(k_cm_knn_fill<6>); break;
-                    case 7: wave ? fill(k_cm_knn_fill_wave<7>) : fill(k_cm_knn_fill<7>); break;
-                    default: wave ? fill(k_cm_knn_fill_wave<8>) : fill(k_cm_knn_fill<8>); break;
-                }
-            }
-        }
-        if (!rc && hipGetLastError() != hipSuccess) fail("mqr_color_map: kernel launch failed");
+        if (hipGetLastError() != hipSuccess) fail("mqr_color_map: kernel launch failed");
+        if (!rc) rc = cm_finish_colors(device, s, dV, nv, avg, cnt, knn, dO, "mqr_color_map");
         if (!rc && out_loc != MQR_DEVICE &&
             (copy_to_host(device, colors_out, dO, sizeof(float) * 3 * nv, s) ||
              (counts_out && copy_to_host(device, counts_out, cnt, sizeof(int32_t) * nv, s))))

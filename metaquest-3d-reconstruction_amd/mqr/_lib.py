@@ -155,6 +155,20 @@ SIGNATURES = {
                                                       ctypes.c_int, _f64p, ctypes.c_int, _i32p, _i32p, _f64p,
                                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, _f64p,
                                                       _i64p]),
+    "mqr_colormap_create": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _f64p, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                           ctypes.c_double, ctypes.POINTER(_vp)]),
+    "mqr_colormap_counts": (ctypes.c_int, [_vp, _i64p]),
+    "mqr_colormap_set_poses": (ctypes.c_int, [_vp, _f64p]),
+    "mqr_colormap_get_poses": (ctypes.c_int, [_vp, _f64p]),
+    "mqr_colormap_proxy": (ctypes.c_int, [_vp, _f64p]),
+    "mqr_colormap_systems": (ctypes.c_int, [_vp, _f64p, _f64p, _f64p, _i64p]),
+    "mqr_colormap_optimize": (ctypes.c_int, [_vp, ctypes.c_int, _f64p, _i64p]),
+    "mqr_colormap_colors": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    "mqr_colormap_optimize_ms": (ctypes.c_int, [_vp, _f32p]),
+    "mqr_colormap_build_tag": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
+    "mqr_colormap_destroy": (ctypes.c_int, [_vp]),
 }
 
 _lib = None
@@ -252,7 +266,7 @@ ORDERED = frozenset({
     "mqr_color_map", "mqr_scene_add_triangles", "mqr_scene_cast_pinhole", "mqr_scene_cast_rays",
     "mqr_mesh_filter_components", "mqr_memcpy",
     "mqr_cloudset_create", "mqr_cloudset_voxel_down", "mqr_evaluate_pairs", "mqr_icp_pairs", "mqr_information_pairs",
-    "mqr_odometry_information_pairs",
+    "mqr_odometry_information_pairs", "mqr_colormap_create", "mqr_colormap_colors",
 })
 _tls = threading.local()
 

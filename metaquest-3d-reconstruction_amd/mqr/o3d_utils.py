@@ -100,6 +100,28 @@ def convert_pose_graph_to_transforms(pose_graph):
     return Transforms(CoordinateSystem.OPEN3D, matrices[:, :3, 3], quats)
 
 
+def dataset_intrinsics_extrinsics(dataset):
+    """(K (N,3,3), T_wc (N,4,4)) float64 of a camera dataset: what convert_dataset_to_trajectory
+    (o3d_utils.py:38-76) puts into its PinholeCameraParameters -- the intrinsics with the cx flip and
+    the world->camera matrices of the transforms converted to the OPEN3D camera convention."""
+    from .models import CoordinateSystem
+    K = np.asarray(compute_o3d_intrinsic_matrices(dataset), np.float64).reshape(-1, 3, 3)
+    T = dataset.transforms.convert_coordinate_system(target_coordinate_system=CoordinateSystem.OPEN3D,
+                                                     is_camera=True).extrinsics_wc
+    return K, np.asarray(T, np.float64).reshape(-1, 4, 4)
+
+
+def extrinsics_to_transforms(T_wc):
+    """OPEN3D Transforms of world->camera matrices (N,4,4): each inverted, position and quaternion of
+    the pose, as convert_trajectory_to_transforms does (o3d_utils.py:79-96)."""
+    from scipy.spatial.transform import Rotation
+    from .models import CoordinateSystem, Transforms
+    T = np.asarray(T_wc, np.float64).reshape(-1, 4, 4)
+    poses = np.stack([np.linalg.inv(m) for m in T]) if len(T) else np.zeros((0, 4, 4))
+    quats = Rotation.from_matrix(poses[:, :3, :3]).as_quat() if len(T) else np.zeros((0, 4))
+    return Transforms(CoordinateSystem.OPEN3D, poses[:, :3, 3].copy(), quats)
+
+
 def _masked_depth(depth_data_io, side, index, dataset, use_confidence_filtered_depth, confidence_threshold,
                   valid_count_threshold, warn=print) -> Optional[np.ndarray]:
     depth = depth_data_io.load_depth_map(side=side, timestamp=dataset.timestamps[index],

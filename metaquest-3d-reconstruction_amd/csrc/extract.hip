@@ -1586,6 +1586,8 @@ int mqr_vbg_set_extract_mode(mqr_vbg* v, int mode) {
 int mqr_extract_mesh_owned(mqr_vbg* v, float thr, int64_t n_owned, mqr_geom** out) {
     MQR_REQUIRE(v && out, "null argument");
     MQR_REQUIRE(v->R <= kMaxR, "extract_triangle_mesh supports block_resolution <= 16");
+    // (at R = 1 the tile [-1, R + 1] would reach two blocks away)
+    MQR_REQUIRE(v->R >= 2, "extract_triangle_mesh needs block_resolution >= 2, got " + std::to_string(v->R));
     MQR_REQUIRE(n_owned < 0 || v->R == 16 || v->R == 8, "owned-block extraction supports block_resolution 8 / 16");
     const int64_t tri_blocks = n_owned < 0 ? INT64_MAX : n_owned;
     MQR_CHECK_HIP(hipSetDevice(v->device));
@@ -1615,6 +1617,7 @@ int mqr_extract_mesh_owned(mqr_vbg* v, float thr, int64_t n_owned, mqr_geom** ou
 int mqr_extract_points(mqr_vbg* v, float thr, mqr_geom** out) {
     MQR_REQUIRE(v && out, "null argument");
     MQR_REQUIRE(v->R <= kMaxR, "extract_point_cloud supports block_resolution <= 16");
+    MQR_REQUIRE(v->R >= 2, "extract_point_cloud needs block_resolution >= 2, got " + std::to_string(v->R));
     MQR_CHECK_HIP(hipSetDevice(v->device));
     if (order_after_integrate(v)) return 1;
     const int64_t n = v->pool_count;

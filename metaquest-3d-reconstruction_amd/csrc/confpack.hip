@@ -16,6 +16,7 @@
 #include <cstdint>
 #include <mutex>
 
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 
 namespace {
@@ -41,24 +42,12 @@ __global__ __launch_bounds__(256) void k_pack_counts(const double* __restrict__ 
 struct PackCtx {
     std::mutex mu;
     hipStream_t s = nullptr;
-    void* maps = nullptr;  // [conf f64][valid i32] of the last call
-    size_t maps_cap = 0;
-    uint16_t* packed = nullptr;
-    size_t packed_cap = 0;
+    mqr::GrowBuf maps;    // [conf f64][valid i32] of the last call
+    mqr::GrowBuf packed;  // [uint16] of the last call
     uint32_t* d_bad = nullptr;
     uint32_t* h_bad = nullptr;
 };
-PackCtx g_pack[64];
-
-int grow(void** p, size_t* cap, size_t want) {
-    if (*cap >= want) return 0;
-    if (*p) MQR_CHECK_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    MQR_CHECK_HIP(hipMalloc(p, want));
-    *cap = want;
-    return 0;
-}
+PackCtx g_pack[mqr::kMaxDevices];
 
 }  // namespace
 
@@ -69,7 +58,7 @@ int mqr_confidence_counts(int device, const float* depths, int depth_loc, int N,
                           int ref_end, int frame_range, double depth_max, double error_threshold, uint16_t* counts,
                           int* packed) {
     MQR_REQUIRE(counts && packed, "null argument");
-    MQR_REQUIRE(device >= 0 && device < 64, "bad device");
+    MQR_REQUIRE(device >= 0 && device < mqr::kMaxDevices, "bad device");
     MQR_REQUIRE(N > 0 && H > 0 && W > 0 && ref_begin >= 0 && ref_begin <= ref_end && ref_end <= N, "bad shape");
     *packed = 0;
     const int64_t n = (int64_t)(ref_end - ref_begin) * H * W;
@@ -83,24 +72,24 @@ int mqr_confidence_counts(int device, const float* depths, int depth_loc, int N,
     if (!c.s) MQR_CHECK_HIP(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
     if (!c.d_bad) MQR_CHECK_HIP(hipMalloc(&c.d_bad, sizeof(uint32_t)));
     if (!c.h_bad) MQR_CHECK_HIP(hipHostMalloc(&c.h_bad, sizeof(uint32_t), hipHostMallocDefault));
-    const size_t bc = (sizeof(double) * n + 255) & ~size_t(255);
-    if (grow(&c.maps, &c.maps_cap, bc + sizeof(int32_t) * n) ||
-        grow(reinterpret_cast<void**>(&c.packed), &c.packed_cap, sizeof(uint16_t) * n))
-        return 1;
-    double* dconf = static_cast<double*>(c.maps);
-    int32_t* dvalid = reinterpret_cast<int32_t*>(static_cast<char*>(c.maps) + bc);
+    const size_t bc = mqr::al256(sizeof(double) * n), bm = bc + sizeof(int32_t) * n, bp = sizeof(uint16_t) * n;
+    MQR_CHECK_HIP(c.maps.reserve(bm, bm));
+    MQR_CHECK_HIP(c.packed.reserve(bp, bp));
+    double* dconf = c.maps.as<double>();
+    int32_t* dvalid = reinterpret_cast<int32_t*>(c.maps.as<char>() + bc);
+    uint16_t* dpacked = c.packed.as<uint16_t>();
     // the maps into HBM (mqr_confidence orders itself after the caller's stream and returns complete)
     if (int rc = mqr_confidence(device, depths, depth_loc, N, H, W, K, T_cw, T_cw_inv, frame_ok, ref_begin, ref_end,
                                 frame_range, depth_max, error_threshold, dconf, dvalid, MQR_DEVICE))
         return rc;
     MQR_CHECK_HIP(hipMemsetAsync(c.d_bad, 0, sizeof(uint32_t), c.s));
     const unsigned blocks = (unsigned)std::min<int64_t>((n + 255) / 256, 256 * 32);
-    hipLaunchKernelGGL(k_pack_counts, dim3(blocks), dim3(256), 0, c.s, dconf, dvalid, n, c.packed, c.d_bad);
+    hipLaunchKernelGGL(k_pack_counts, dim3(blocks), dim3(256), 0, c.s, dconf, dvalid, n, dpacked, c.d_bad);
     MQR_CHECK_HIP(hipGetLastError());
     MQR_CHECK_HIP(hipMemcpyAsync(c.h_bad, c.d_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, c.s));
     MQR_CHECK_HIP(hipStreamSynchronize(c.s));
     if (*c.h_bad) return 0;  // not representable: *packed stays 0 (the caller then runs mqr_confidence itself)
-    if (mqr::copy_to_host(device, counts, c.packed, sizeof(uint16_t) * n, c.s)) return 1;
+    if (mqr::copy_to_host(device, counts, dpacked, sizeof(uint16_t) * n, c.s)) return 1;
     MQR_CHECK_HIP(hipStreamSynchronize(c.s));
     *packed = 1;
     return 0;

@@ -1,7 +1,9 @@
-// device_block.hpp -- per-call device staging from the process's device-block cache (geom_block_alloc /
-// geom_block_release, csrc/extract.hip): one block carved into 256-byte aligned pieces and returned to the
-// cache at scope exit, instead of a hipMalloc / hipFree pair per array per call (hipFree synchronises the
-// device; fresh allocations map pages).  The owner synchronises its stream before the scope ends.
+// device_block.hpp -- the library's device memory helpers (csrc/devmem.hip): per-call device staging from the
+// process's device-block cache (geom_block_alloc / geom_block_release): one block carved into 256-byte
+// aligned pieces and returned to the cache at scope exit, instead of a hipMalloc / hipFree pair per array
+// per call (hipFree synchronises the device; fresh allocations map pages).  The owner synchronises its
+// stream before the scope ends.  Also the grow-only buffer every module keeps between calls (GrowBuf) and
+// the carve of a geometry result (geom_alloc).
 #pragma once
 
 #include <algorithm>
@@ -11,7 +13,9 @@
 
 namespace mqr {
 
-inline size_t block_al256(size_t x) { return (x + 255) & ~size_t(255); }
+constexpr int kMaxDevices = 64;  // size of every per-device table (the index is checked against it)
+
+inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct CachedBlock {
     int device;
@@ -23,11 +27,28 @@ struct CachedBlock {
     CachedBlock& operator=(const CachedBlock&) = delete;
     // the next piece of b bytes, or nullptr when the block is missing or full
     void* take(size_t b) {
-        if (!p || used + block_al256(b) > cap) return nullptr;
+        if (!p || used + al256(b) > cap) return nullptr;
         char* r = static_cast<char*>(p) + used;
-        used += block_al256(b);
+        used += al256(b);
         return r;
     }
 };
+
+// Grow-only device buffer, kept between calls by its owner (which also frees it, if ever).  A buffer is
+// regrown through hipFree, which waits for the device, so work a failed call left queued has finished with
+// it: regrowing under queued work is safe.
+struct GrowBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    // cap >= need on success.  A regrow frees the old buffer and allocates max(need, alloc_bytes) (the
+    // caller's growth rule); when that fails the sticky HIP error is cleared and p = nullptr, cap = 0.
+    hipError_t reserve(size_t need, size_t alloc_bytes);
+    template <class T>
+    T* as() const { return static_cast<T*>(p); }
+};
+
+// One cached block for the positions, normals and triangles of a geometry result, recycled across results
+// (geom_block_alloc; mqr_geom_free returns it).  Non-zero with the error set when the device is out of memory.
+int geom_alloc(mqr_geom* g, int64_t nv, int64_t nt);
 
 }  // namespace mqr

@@ -21,18 +21,16 @@
 //   k_mc_emit   blocks with output only: vertices with tsdf values gathered from the pool,
 //               triangles at their global offsets (latency: ~4 dependent load phases per block)
 //   other R: the byte-tile kernels (k_mesh_count / k_mesh_emit) stage (tsdf, flags) tiles.
+//
+// Only extraction lives here.  The result handle (mqr_geom_*), the cached device block it is carved from
+// (geom_alloc) and the copies to the host are in devmem.hip.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cstdlib>
+#include <string>
 
-#include <atomic>
-#include <cstring>
-#include <mutex>
-#include <thread>
-#include <tuple>
-#include <vector>
-
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 #include "mqr_mc_tables.h"
 
@@ -1262,8 +1260,6 @@ __global__ __launch_bounds__(kThreads) void k_points(const int32_t* __restrict__
 
 
 // ---------------------------------------------------------------- host side
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // Carve the grow-only per-volume scratch: nb[27n], 4 count/offset arrays of n, faces[3R^2 n], scan temp.
 struct ExScratch {
     int32_t *nb, *c0, *c1, *o0, *o1;
@@ -1277,25 +1273,24 @@ static int ex_scratch(mqr_vbg* v, int64_t n, bool mesh, ExScratch& e) {
     size_t tmp_bytes = 0;
     MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)nullptr, (int32_t*)nullptr,
                                                    (int)n, v->stream));
-    const size_t sz_nb = align256(sizeof(int32_t) * 27 * n), sz_c = align256(sizeof(int32_t) * n);
+    const size_t sz_nb = al256(sizeof(int32_t) * 27 * n), sz_c = al256(sizeof(int32_t) * n);
     // mesh: the byte-tile path's face tables (3 R^2 u32 per block), or the bit-row path's row records
     // (R^2 uint4), sign rows ((R + 2)^2 u32) and per-cube triangle counts (R^2 u64) per block,
     // whichever is larger
-    const size_t sz_f = mesh ? align256(std::max(sizeof(uint32_t) * 3 * v->R * v->R,
-                                                 sizeof(uint32_t) * (6 * v->R * v->R + (v->R + 2) * (v->R + 2))) *
-                                        n)
+    const size_t sz_f = mesh ? al256(std::max(sizeof(uint32_t) * 3 * v->R * v->R,
+                                              sizeof(uint32_t) * (6 * v->R * v->R + (v->R + 2) * (v->R + 2))) *
+                                     n)
                              : 0;
-    const size_t sz_b = align256(sizeof(uint16_t) * 3 * v->R * v->R * n);
+    const size_t sz_b = al256(sizeof(uint16_t) * 3 * v->R * v->R * n);
     tmp_bytes = std::max<size_t>(tmp_bytes, 2 * sizeof(int64_t));
-    const size_t need = sz_nb + 4 * sz_c + sz_f + sz_b + align256(tmp_bytes);
+    const size_t need = sz_nb + 4 * sz_c + sz_f + sz_b + al256(tmp_bytes);
     if (v->ex_scratch_bytes < need) {
         MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
-        if (v->ex_scratch) MQR_CHECK_HIP(hipFree(v->ex_scratch));
-        v->ex_scratch = nullptr;
-        v->ex_scratch_bytes = 0;
-        const size_t cap = need + need / 4;
-        MQR_CHECK_HIP(hipMalloc(&v->ex_scratch, cap));
-        v->ex_scratch_bytes = cap;
+        GrowBuf b{v->ex_scratch, v->ex_scratch_bytes};  // the volume holds the pair as two plain fields
+        const hipError_t ex_scratch_alloc = b.reserve(need, need + need / 4);
+        v->ex_scratch = b.p;
+        v->ex_scratch_bytes = b.cap;
+        MQR_CHECK_HIP(ex_scratch_alloc);
     }
     // fine-grained (coherent) pinned memory: k_scan_counts writes the totals straight into it (ex_mode bit 2)
     if (!v->h_ex) MQR_CHECK_HIP(hipHostMalloc(&v->h_ex, 4 * sizeof(int64_t), hipHostMallocCoherent));
@@ -1332,59 +1327,6 @@ static int scan_totals(mqr_vbg* v, const ExScratch& e, int64_t n, int arrays, in
     MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
     *tot0 = (int64_t)h[0] + h[1];
     if (arrays > 1) *tot1 = (int64_t)h[2] + h[3];
-    return 0;
-}
-
-static std::mutex g_geom_mu;
-static std::vector<std::tuple<int, void*, size_t>> g_geom_cache;  // (device, block, capacity)
-constexpr size_t kGeomCacheBlocks = 4;
-
-void* geom_block_alloc(int device, size_t bytes, size_t* cap) {
-    {
-        std::lock_guard<std::mutex> lk(g_geom_mu);
-        int best = -1;
-        for (size_t i = 0; i < g_geom_cache.size(); ++i) {
-            const auto& e = g_geom_cache[i];
-            if (std::get<0>(e) == device && std::get<2>(e) >= bytes &&
-                (best < 0 || std::get<2>(e) < std::get<2>(g_geom_cache[best])))
-                best = (int)i;
-        }
-        if (best >= 0) {
-            void* p = std::get<1>(g_geom_cache[best]);
-            *cap = std::get<2>(g_geom_cache[best]);
-            g_geom_cache.erase(g_geom_cache.begin() + best);
-            return p;
-        }
-    }
-    const size_t want = (bytes + (size_t(1) << 20) - 1) & ~((size_t(1) << 20) - 1);
-    void* p = nullptr;
-    if (hipMalloc(&p, want) != hipSuccess) return nullptr;
-    *cap = want;
-    return p;
-}
-
-void geom_block_release(int device, void* p, size_t cap) {
-    if (!p) return;
-    {
-        std::lock_guard<std::mutex> lk(g_geom_mu);
-        if (cap && g_geom_cache.size() < kGeomCacheBlocks) {
-            g_geom_cache.emplace_back(device, p, cap);
-            return;
-        }
-    }
-    (void)hipFree(p);
-}
-
-// One allocation for positions, normals and triangles, recycled across results (geom_block_alloc).
-static int alloc_geom(mqr_geom* g, int64_t nv, int64_t nt) {
-    const size_t sv = align256(sizeof(float) * 3 * std::max<int64_t>(nv, 1));
-    const size_t st = align256(sizeof(int32_t) * 3 * std::max<int64_t>(nt, 1));
-    g->blk = geom_block_alloc(g->device, 2 * sv + st, &g->blk_cap);
-    MQR_REQUIRE(g->blk, "geometry: device allocation failed");
-    char* p = static_cast<char*>(g->blk);
-    g->pos = reinterpret_cast<float*>(p);
-    g->nrm = reinterpret_cast<float*>(p + sv);
-    g->tri = reinterpret_cast<int32_t*>(p + 2 * sv);
     return 0;
 }
 
@@ -1465,7 +1407,7 @@ static int mesh_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g, i
         // into exact buffers if the totals exceed it.  Without, wait for the totals first.
         int64_t cv = spec_cap(v->ex_hint[0]), ct = spec_cap(v->ex_hint[1]);
         const bool spec = cv > 0 && ct > 0;
-        if (spec && alloc_geom(g, cv, ct)) return 1;
+        if (spec && geom_alloc(g, cv, ct)) return 1;
         MQR_CHECK_HIP(hipGetLastError());
         if (!direct) MQR_CHECK_HIP(hipMemcpyAsync(v->h_ex, tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, v->stream));
         bool emitted = false;
@@ -1490,7 +1432,7 @@ static int mesh_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g, i
             geom_block_release(g->device, g->blk, g->blk_cap);
             g->blk = nullptr;
         }
-        if (alloc_geom(g, nv, nt)) return 1;
+        if (geom_alloc(g, nv, nt)) return 1;
         launch_mc_emit<RT>(v, n, (const int32_t*)e.nb, (const uint64_t*)v->bkeys, (const float2*)v->pool, v->voxel_size,
                            (const int32_t*)e.c0, (const int32_t*)e.c1, (const int32_t*)e.o0, (const int32_t*)e.o1,
                            (const uint4*)rows4, (const uint32_t*)rowNt, g->pos, g->nrm, g->tri, nv, nt,
@@ -1504,7 +1446,7 @@ static int mesh_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g, i
         MQR_REQUIRE(nv < (int64_t)1 << 31 && nt < (int64_t)1 << 31, "mesh exceeds int32 vertex / triangle ids");
         g->nv = nv;
         g->nt = nt;
-        if (alloc_geom(g, nv, nt)) return 1;
+        if (geom_alloc(g, nv, nt)) return 1;
         hipLaunchKernelGGL(k_mesh_emit<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->bkeys,
                            v->pool, v->R, v->voxel_size, thr, e.c0, e.c1, e.o0, e.o1, e.faces, g->pos, g->nrm, g->tri);
     }
@@ -1531,7 +1473,7 @@ static int point_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g) 
         if (!direct) MQR_CHECK_HIP(hipMemcpyAsync(v->h_ex, tot, sizeof(int64_t), hipMemcpyDeviceToHost, v->stream));
         const int64_t cp = spec_cap(v->ex_hint[2]);  // speculative capacity, as in mesh_passes
         if (cp > 0) {
-            if (alloc_geom(g, cp, 0)) return 1;
+            if (geom_alloc(g, cp, 0)) return 1;
             hipLaunchKernelGGL(k_pt_emit<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys,
                                v->pool, v->voxel_size, e.c0, e.o0, reinterpret_cast<const uint4*>(e.faces), g->pos,
                                g->nrm, cp);
@@ -1547,7 +1489,7 @@ static int point_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g) 
             geom_block_release(g->device, g->blk, g->blk_cap);
             g->blk = nullptr;
         }
-        if (alloc_geom(g, np, 0)) return 1;
+        if (geom_alloc(g, np, 0)) return 1;
         hipLaunchKernelGGL(k_pt_emit<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys, v->pool,
                            v->voxel_size, e.c0, e.o0, reinterpret_cast<const uint4*>(e.faces), g->pos, g->nrm, np);
     } else {
@@ -1557,7 +1499,7 @@ static int point_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g) 
         MQR_CHECK_HIP(hipGetLastError());
         if (scan_totals(v, e, n, 1, &np, nullptr)) return 1;
         g->nv = np;
-        if (alloc_geom(g, np, 0)) return 1;
+        if (geom_alloc(g, np, 0)) return 1;
         hipLaunchKernelGGL(k_points<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->bkeys, v->pool,
                            v->R, v->voxel_size, thr, e.c0, e.o0, g->pos, g->nrm);
     }
@@ -1638,210 +1580,6 @@ int mqr_extract_points(mqr_vbg* v, float thr, mqr_geom** out) {
         return rc;
     }
     *out = g;
-    return 0;
-}
-
-int mqr_geom_counts(mqr_geom* g, int64_t* nv, int64_t* nt) {
-    MQR_REQUIRE(g, "null geometry");
-    if (nv) *nv = g->nv;
-    if (nt) *nt = g->nt;
-    return 0;
-}
-
-}  // extern "C"
-
-namespace mqr {
-// Device -> pageable host copies of large results (mqr_geom_copy, mqr_memcpy).  hipMemcpy into pageable
-// memory stages through the runtime's pinned buffers on the calling thread: ~10 GB/s for the 1 GB C5 mesh
-// (BENCH_r04 c5.extract_ms 102.9 ms).  Here a copy kernel moves the range chunk by chunk into a ring of
-// pinned slots (GPU stores over the fabric: 54.7 GB/s into pinned memory, SDMA 57.1, tools/d2h_modes.hip)
-// on a stream the process already runs, and kD2HThreads host threads copy each slot out as its event
-// completes (first-touching the destination pages in parallel).  Round 5's first version gave every host
-// thread its own stream and DMA: the same ~41 GB/s once set up, but its set-up cost the process's first
-// large copy 46.6 ms (first 48 MB copy, vs 1.6 ms for the second, tools/d2h_probe.py) -- four stream
-// creations 50 ms and the copy engine's first use 16-19 ms on an MI355X box (tools/d2h_setup_probe.hip,
-// profiles/r05_d2h_setup_probe.json).  The ring (one pinned allocation per device) is kept and the calls
-// are serialised by a mutex: one large copy at a time per process.
-constexpr int kD2HThreads = 8;  // 1 GiB into a fresh array: 44.4 GB/s with 4, 51.1 with 8 (profiles/r05_d2h_probe.jsonl)
-constexpr int kD2HSlots = 8;
-constexpr size_t kD2HChunk = size_t(8) << 20;
-constexpr int kD2HDevices = 64;
-struct D2HRing {
-    char* buf = nullptr;
-    hipEvent_t ev[kD2HSlots] = {};
-};
-static std::mutex g_d2h_mu;
-static D2HRing g_d2h[kD2HDevices];
-
-__global__ __launch_bounds__(256) void k_copy_out16(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t n16) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-
-__global__ __launch_bounds__(256) void k_copy_out1(uint8_t* __restrict__ dst, const uint8_t* __restrict__ src, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-
-hipStream_t copy_stream(int device) {
-    if (caller_stream()) {
-        hipDevice_t sd = -1;
-        const bool same = hipStreamGetDevice(caller_stream(), &sd) == hipSuccess && sd == device;
-        (void)hipGetLastError();
-        if (same) return caller_stream();
-    }
-    return nullptr;
-}
-
-static void launch_copy(char* to, const char* from, size_t len, hipStream_t s) {
-    const bool aligned = ((reinterpret_cast<uintptr_t>(to) | reinterpret_cast<uintptr_t>(from)) & 15) == 0;
-    const size_t n16 = aligned ? len / 16 : 0, tail = len - 16 * n16;
-    if (n16) k_copy_out16<<<1024, 256, 0, s>>>(reinterpret_cast<uint4*>(to), reinterpret_cast<const uint4*>(from), n16);
-    if (tail)
-        k_copy_out1<<<(unsigned)std::min<size_t>(1024, (tail + 255) / 256), 256, 0, s>>>(
-            reinterpret_cast<uint8_t*>(to) + 16 * n16, reinterpret_cast<const uint8_t*>(from) + 16 * n16, tail);
-}
-
-// One ring transfer: the GPU fills slot k % S with chunk k, host thread k % T copies it out once its
-// event completes; this thread queues the GPU copies in chunk order, each into a slot whose previous
-// chunk has been copied out.
-static int ring_copy(int device, char* dst, const char* src, size_t bytes, hipStream_t s) {
-    MQR_REQUIRE(device >= 0 && device < kD2HDevices, "device index out of range");
-    std::lock_guard<std::mutex> lk(g_d2h_mu);
-    D2HRing& r = g_d2h[device];
-    if (!r.buf) {
-        MQR_CHECK_HIP(hipHostMalloc(reinterpret_cast<void**>(&r.buf), kD2HSlots * kD2HChunk, hipHostMallocDefault));
-        for (auto& e : r.ev) MQR_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const size_t nchunks = (bytes + kD2HChunk - 1) / kD2HChunk;
-    // MQR_D2H_THREADS (1..8): another thread count, for tools/d2h_probe.py
-    static const int env_threads =
-        getenv("MQR_D2H_THREADS") ? std::max(1, std::min(8, atoi(getenv("MQR_D2H_THREADS")))) : kD2HThreads;
-    const int T = (int)std::min<size_t>(env_threads, nchunks);
-    auto len_of = [&](size_t k) { return std::min(kD2HChunk, bytes - k * kD2HChunk); };
-    std::atomic<int64_t> issued{0};            // chunks whose GPU copy and event are queued
-    std::atomic<int64_t> host_done[kD2HSlots];  // the last chunk copied out of each slot
-    for (auto& d : host_done) d.store(-1);
-    std::atomic<int> failed{0};
-    std::vector<std::string> errs(T + 1);
-    auto host_side = [&](int t) {
-        for (size_t k = (size_t)t; k < nchunks; k += (size_t)T) {
-            while (issued.load(std::memory_order_acquire) <= (int64_t)k && !failed.load()) std::this_thread::yield();
-            if (failed.load()) return;
-            const int slot = (int)(k % kD2HSlots);
-            hipError_t e = hipEventSynchronize(r.ev[slot]);
-            if (e != hipSuccess) {
-                errs[t] = std::string("host copy: hipEventSynchronize: ") + hipGetErrorString(e);
-                failed.store(1);
-                return;
-            }
-            std::memcpy(dst + k * kD2HChunk, r.buf + slot * kD2HChunk, len_of(k));
-            host_done[slot].store((int64_t)k, std::memory_order_release);
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t) th.emplace_back(host_side, t);
-    for (size_t k = 0; k < nchunks && !failed.load(); ++k) {
-        const int slot = (int)(k % kD2HSlots);
-        if (k >= (size_t)kD2HSlots)
-            while (host_done[slot].load(std::memory_order_acquire) != (int64_t)(k - kD2HSlots) && !failed.load())
-                std::this_thread::yield();
-        if (failed.load()) break;
-        launch_copy(r.buf + slot * kD2HChunk, src + k * kD2HChunk, len_of(k), s);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess) e = hipEventRecord(r.ev[slot], s);
-        if (e != hipSuccess) {
-            errs[T] = std::string("host copy: chunk copy launch: ") + hipGetErrorString(e);
-            failed.store(1);
-            break;
-        }
-        issued.store((int64_t)k + 1, std::memory_order_release);
-    }
-    for (auto& x : th) x.join();
-    if (failed.load()) {
-        (void)hipStreamSynchronize(s);  // no slot write left in flight for the next call
-        for (auto& m : errs)
-            if (!m.empty()) {
-                set_error(m);
-                return 1;
-            }
-    }
-    return 0;
-}
-
-int d2h_parallel(int device, void* dst, const void* src, size_t bytes) {
-    return copy_to_host(device, dst, src, bytes, copy_stream(device));
-}
-
-// page-locked host memory (hipHostMalloc / hipHostRegister, e.g. torch's pin_memory()): the DMA engine
-// reads or writes it directly, no staging
-static bool host_pinned(const void* p) {
-    hipPointerAttribute_t a{};
-    const bool pinned = hipPointerGetAttributes(&a, p) == hipSuccess && a.type == hipMemoryTypeHost;
-    (void)hipGetLastError();
-    return pinned;
-}
-
-int copy_to_host(int device, void* dst, const void* src, size_t bytes, hipStream_t s) {
-    if (bytes >= kD2HParallelMin && !host_pinned(dst)) return ring_copy(device, static_cast<char*>(dst), static_cast<const char*>(src), bytes, s);
-    if (bytes) {
-        MQR_CHECK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
-        MQR_CHECK_HIP(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-
-// uploads: HIP's own pageable path already runs at the link's rate from present pages (1 GiB: 55.8 GB/s,
-// against 44.1 through a ring like the one above, profiles/r05_d2h_probe.jsonl)
-int copy_to_device(int device, void* dst, const void* src, size_t bytes, hipStream_t s) {
-    (void)device;
-    if (bytes) {
-        MQR_CHECK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-        MQR_CHECK_HIP(hipStreamSynchronize(s));
-    }
-    return 0;
-}
-
-static int geom_copy_one(int device, void* dst, const void* src, size_t bytes, hipMemcpyKind k) {
-    if (k == hipMemcpyDeviceToHost && bytes >= kD2HParallelMin) return d2h_parallel(device, dst, src, bytes);
-    MQR_CHECK_HIP(hipMemcpy(dst, src, bytes, k));
-    return 0;
-}
-}  // namespace mqr
-
-extern "C" {
-
-int mqr_geom_copy(mqr_geom* g, float* positions, float* normals, int32_t* triangles, int loc) {
-    MQR_REQUIRE(g, "null geometry");
-    MQR_CHECK_HIP(hipSetDevice(g->device));
-    const hipMemcpyKind k = loc == MQR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    // hipMemcpy orders after the null stream only: the caller's stream may still use the buffers
-    if (loc == MQR_DEVICE && caller_stream()) MQR_CHECK_HIP(hipStreamSynchronize(caller_stream()));
-    if (positions && g->nv && geom_copy_one(g->device, positions, g->pos, sizeof(float) * 3 * g->nv, k)) return 1;
-    if (normals && g->nv && geom_copy_one(g->device, normals, g->nrm, sizeof(float) * 3 * g->nv, k)) return 1;
-    if (triangles && g->nt && geom_copy_one(g->device, triangles, g->tri, sizeof(int32_t) * 3 * g->nt, k)) return 1;
-    return 0;
-}
-
-int mqr_geom_device_ptrs(mqr_geom* g, void** positions, void** normals, void** triangles) {
-    MQR_REQUIRE(g, "null geometry");
-    if (positions) *positions = g->nv ? g->pos : nullptr;
-    if (normals) *normals = g->nv ? g->nrm : nullptr;
-    if (triangles) *triangles = g->nt ? g->tri : nullptr;
-    return 0;
-}
-
-int mqr_geom_free(mqr_geom* g) {
-    if (!g) return 0;
-    (void)hipSetDevice(g->device);
-    if (g->blk) {
-        // the block may still be read by work queued on a stream (a device-side copy): drain first
-        (void)hipDeviceSynchronize();
-        geom_block_release(g->device, g->blk, g->blk_cap);
-    } else {
-        if (g->pos) (void)hipFree(g->pos);
-        if (g->nrm) (void)hipFree(g->nrm);
-        if (g->tri) (void)hipFree(g->tri);
-    }
-    delete g;
     return 0;
 }
 

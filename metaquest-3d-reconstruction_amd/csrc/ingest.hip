@@ -21,6 +21,7 @@
 #include <mutex>
 #include <vector>
 
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 
 namespace mqr {
@@ -139,48 +140,37 @@ __global__ __launch_bounds__(256) void k_decode_depth(const float* __restrict__ 
 struct DecodeCtx {
     std::mutex mu;
     hipStream_t s = nullptr;
-    char* scratch = nullptr;
-    size_t scratch_cap = 0;
-    DecodeFrame* d_fr = nullptr;
-    uint32_t* d_flags = nullptr;
+    GrowBuf scratch;
+    GrowBuf d_fr;     // DecodeFrame[frame_cap]
+    GrowBuf d_flags;  // uint32_t[frame_cap]
     DecodeFrame* h_fr = nullptr;
     uint32_t* h_flags = nullptr;
-    int frame_cap = 0;
+    int frame_cap = 0;  // of the pinned mirrors (the device arrays hold at least as many)
 };
-static DecodeCtx g_decode[64];
+static DecodeCtx g_decode[kMaxDevices];
 
 static int decode_ctx_reserve(DecodeCtx& c, size_t scratch_bytes, int frames) {
     if (!c.s) MQR_CHECK_HIP(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
-    if (scratch_bytes > c.scratch_cap) {
+    if (scratch_bytes > c.scratch.cap) {
         MQR_CHECK_HIP(hipStreamSynchronize(c.s));
-        if (c.scratch) MQR_CHECK_HIP(hipFree(c.scratch));
-        c.scratch = nullptr;
-        c.scratch_cap = 0;
-        MQR_CHECK_HIP(hipMalloc(&c.scratch, scratch_bytes));
-        c.scratch_cap = scratch_bytes;
+        MQR_CHECK_HIP(c.scratch.reserve(scratch_bytes, scratch_bytes));
     }
     if (frames > c.frame_cap) {
         MQR_CHECK_HIP(hipStreamSynchronize(c.s));
-        const int cap = std::max(frames, 256);
-        if (c.d_fr) MQR_CHECK_HIP(hipFree(c.d_fr));
-        if (c.d_flags) MQR_CHECK_HIP(hipFree(c.d_flags));
+        const size_t cap = (size_t)std::max(frames, 256);
         if (c.h_fr) MQR_CHECK_HIP(hipHostFree(c.h_fr));
         if (c.h_flags) MQR_CHECK_HIP(hipHostFree(c.h_flags));
-        c.d_fr = nullptr;
-        c.d_flags = nullptr;
         c.h_fr = nullptr;
         c.h_flags = nullptr;
         c.frame_cap = 0;
-        MQR_CHECK_HIP(hipMalloc(&c.d_fr, sizeof(DecodeFrame) * cap));
-        MQR_CHECK_HIP(hipMalloc(&c.d_flags, sizeof(uint32_t) * cap));
+        MQR_CHECK_HIP(c.d_fr.reserve(sizeof(DecodeFrame) * cap, sizeof(DecodeFrame) * cap));
+        MQR_CHECK_HIP(c.d_flags.reserve(sizeof(uint32_t) * cap, sizeof(uint32_t) * cap));
         MQR_CHECK_HIP(hipHostMalloc(&c.h_fr, sizeof(DecodeFrame) * cap, hipHostMallocDefault));
         MQR_CHECK_HIP(hipHostMalloc(&c.h_flags, sizeof(uint32_t) * cap, hipHostMallocDefault));
-        c.frame_cap = cap;
+        c.frame_cap = (int)cap;
     }
     return 0;
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 }  // namespace mqr
 
@@ -193,7 +183,7 @@ static int decode_impl(int device, const float* raw, int raw_loc, int N, int H, 
                        float* depth_out, int out_loc, uint8_t* frame_ok) {
     MQR_REQUIRE(raw && nears && fars && depth_out && frame_ok, "null argument");
     MQR_REQUIRE(N >= 0 && H > 0 && W > 0, "bad frame shape");
-    MQR_REQUIRE(device >= 0 && device < 64, "device index out of range");
+    MQR_REQUIRE(device >= 0 && device < kMaxDevices, "device index out of range");
     if (N == 0) return 0;
     const bool any_mask = has_mask && std::any_of(has_mask, has_mask + N, [](uint8_t m) { return m != 0; });
     MQR_REQUIRE(!any_mask || mask8 || (conf && valid_count), "mask requested without confidence maps");
@@ -204,10 +194,10 @@ static int decode_impl(int device, const float* raw, int raw_loc, int N, int H, 
     // scratch layout: [raw f32][conf f64][count i32] or [mask u8] [out f32], only the parts that are staged
     const bool stage_raw = raw_loc != MQR_DEVICE, stage_mask = any_mask && mask_loc != MQR_DEVICE,
                stage_out = out_loc != MQR_DEVICE;
-    const size_t b_raw = stage_raw ? align256(sizeof(float) * total) : 0;
-    const size_t b_conf = stage_mask && !mask8 ? align256(sizeof(double) * total) : 0;
-    const size_t b_vc = stage_mask ? align256((mask8 ? 1 : sizeof(int32_t)) * total) : 0;
-    const size_t b_out = stage_out ? align256(sizeof(float) * total) : 0;
+    const size_t b_raw = stage_raw ? al256(sizeof(float) * total) : 0;
+    const size_t b_conf = stage_mask && !mask8 ? al256(sizeof(double) * total) : 0;
+    const size_t b_vc = stage_mask ? al256((mask8 ? 1 : sizeof(int32_t)) * total) : 0;
+    const size_t b_out = stage_out ? al256(sizeof(float) * total) : 0;
     if (decode_ctx_reserve(c, std::max<size_t>(b_raw + b_conf + b_vc + b_out, 256), N)) return 1;
     if ((!stage_raw || (any_mask && !stage_mask) || !stage_out) && order_after_caller(device, c.s)) return 2;
     for (int f = 0; f < N; ++f) {
@@ -224,7 +214,7 @@ static int decode_impl(int device, const float* raw, int raw_loc, int N, int H, 
         }
         d.mask = any_mask && has_mask[f];
     }
-    char* sp = c.scratch;
+    char* sp = c.scratch.as<char>();
     const float* d_raw = raw;
     if (stage_raw) {
         if (copy_to_device(device, sp, raw, sizeof(float) * total, c.s)) return 1;
@@ -247,8 +237,10 @@ static int decode_impl(int device, const float* raw, int raw_loc, int N, int H, 
         sp += b_vc;
     }
     float* d_out = stage_out ? reinterpret_cast<float*>(sp) : depth_out;
-    MQR_CHECK_HIP(hipMemcpyAsync(c.d_fr, c.h_fr, sizeof(DecodeFrame) * N, hipMemcpyHostToDevice, c.s));
-    MQR_CHECK_HIP(hipMemsetAsync(c.d_flags, 0, sizeof(uint32_t) * N, c.s));
+    DecodeFrame* d_fr = c.d_fr.as<DecodeFrame>();
+    uint32_t* d_flags = c.d_flags.as<uint32_t>();
+    MQR_CHECK_HIP(hipMemcpyAsync(d_fr, c.h_fr, sizeof(DecodeFrame) * N, hipMemcpyHostToDevice, c.s));
+    MQR_CHECK_HIP(hipMemsetAsync(d_flags, 0, sizeof(uint32_t) * N, c.s));
     auto aligned = [](const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; };
     const bool vec = HW % 4 == 0 && aligned(d_raw, 16) && aligned(d_out, 16) &&
                      (!any_mask || (mask8 ? aligned(d_m8, 4) : (aligned(d_conf, 32) && aligned(d_vc, 16))));
@@ -259,19 +251,19 @@ static int decode_impl(int device, const float* raw, int raw_loc, int N, int H, 
     const unsigned gx = (unsigned)std::min<int64_t>((work + 255) / 256, per_frame);
     const dim3 grid(gx, (unsigned)N);
     if (mask8 && vec)
-        hipLaunchKernelGGL((k_decode_depth<true, true>), grid, dim3(256), 0, c.s, d_raw, HW, c.d_fr, nullptr, nullptr,
-                           conf_thr, count_thr, d_out, c.d_flags, d_m8);
+        hipLaunchKernelGGL((k_decode_depth<true, true>), grid, dim3(256), 0, c.s, d_raw, HW, d_fr, nullptr, nullptr,
+                           conf_thr, count_thr, d_out, d_flags, d_m8);
     else if (mask8)
-        hipLaunchKernelGGL((k_decode_depth<false, true>), grid, dim3(256), 0, c.s, d_raw, HW, c.d_fr, nullptr, nullptr,
-                           conf_thr, count_thr, d_out, c.d_flags, d_m8);
+        hipLaunchKernelGGL((k_decode_depth<false, true>), grid, dim3(256), 0, c.s, d_raw, HW, d_fr, nullptr, nullptr,
+                           conf_thr, count_thr, d_out, d_flags, d_m8);
     else if (vec)
-        hipLaunchKernelGGL((k_decode_depth<true, false>), grid, dim3(256), 0, c.s, d_raw, HW, c.d_fr, d_conf, d_vc,
-                           conf_thr, count_thr, d_out, c.d_flags, nullptr);
+        hipLaunchKernelGGL((k_decode_depth<true, false>), grid, dim3(256), 0, c.s, d_raw, HW, d_fr, d_conf, d_vc,
+                           conf_thr, count_thr, d_out, d_flags, nullptr);
     else
-        hipLaunchKernelGGL((k_decode_depth<false, false>), grid, dim3(256), 0, c.s, d_raw, HW, c.d_fr, d_conf, d_vc,
-                           conf_thr, count_thr, d_out, c.d_flags, nullptr);
+        hipLaunchKernelGGL((k_decode_depth<false, false>), grid, dim3(256), 0, c.s, d_raw, HW, d_fr, d_conf, d_vc,
+                           conf_thr, count_thr, d_out, d_flags, nullptr);
     MQR_CHECK_HIP(hipGetLastError());
-    MQR_CHECK_HIP(hipMemcpyAsync(c.h_flags, c.d_flags, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, c.s));
+    MQR_CHECK_HIP(hipMemcpyAsync(c.h_flags, d_flags, sizeof(uint32_t) * N, hipMemcpyDeviceToHost, c.s));
     if (stage_out && copy_to_host(device, depth_out, d_out, sizeof(float) * total, c.s)) return 1;
     MQR_CHECK_HIP(hipStreamSynchronize(c.s));
     for (int f = 0; f < N; ++f) {

@@ -47,6 +47,7 @@
 #include <mutex>
 #include <vector>
 
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 
 // ------------------------------------------------------------------ RCCL, resolved at run time
@@ -114,11 +115,10 @@ namespace mqr {
 // Grow-only device scratch of the merge plan (hipFree synchronises the device: no allocation per
 // merge once the block counts stop growing) and the pinned summary the host reads.
 struct PlanScratch {
-    void* buf = nullptr;
-    size_t cap = 0;
+    GrowBuf buf;
     void* h_sum = nullptr;  // pinned PlanSummary
     ~PlanScratch() {
-        if (buf) (void)hipFree(buf);
+        if (buf.p) (void)hipFree(buf.p);
         if (h_sum) (void)hipHostFree(h_sum);
     }
 };
@@ -132,8 +132,7 @@ struct mqr_comm {
     int device = 0, rank = 0, world = 1;
     ncclComm_t nc = nullptr;
     hipStream_t s = nullptr;
-    void* small = nullptr;  // counts, padded keys
-    size_t small_cap = 0;
+    mqr::GrowBuf small;  // counts, padded keys
     mqr::Exchange* x = nullptr;  // plan, send / receive buffers (grow-only, reused across merges)
     // phase timing of the last merge (mqr_comm_timing): start, plan done, gathered, exchanged, merged
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -488,7 +487,11 @@ struct PlanView {
     uint64_t* out_keys = nullptr;
 };
 
-static size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
+// the merge's grow-only buffers regrow by 1.5x: few reallocations as counts vary
+static int grow(GrowBuf& b, size_t need) {
+    MQR_CHECK_HIP(b.reserve(need, b.cap + b.cap / 2));
+    return 0;
+}
 
 static int device_plan(PlanScratch& S, hipStream_t st, const uint64_t* dkeys, int W, int64_t mx, int me, int mode,
                        int root, PlanView& out) {
@@ -509,7 +512,7 @@ static int device_plan(PlanScratch& S, hipStream_t st, const uint64_t* dkeys, in
     size_t off = 0;
     auto take = [&](size_t bytes) {
         const size_t o = off;
-        off += align_up(bytes);
+        off += al256(bytes);
         return o;
     };
     const size_t o_ks = take(8 * n), o_vi = take(4 * n), o_vs = take(4 * n), o_head = take(4 * n),
@@ -517,16 +520,9 @@ static int device_plan(PlanScratch& S, hipStream_t st, const uint64_t* dkeys, in
                  o_hm = take(8 * n), o_wcnt = take(4 * NC * nwg), o_wbase = take(4 * NC * nwg),
                  o_send = take(4 * nsend), o_rdst = take(4 * n), o_rsrc = take(4 * n), o_okeys = take(8 * n),
                  o_sum = take(sizeof(PlanSummary)), o_tmp = take(tb);
-    if (S.cap < off) {
-        const size_t want = std::max(off, S.cap + S.cap / 2);
-        if (S.buf) MQR_CHECK_HIP(hipFree(S.buf));
-        S.buf = nullptr;
-        S.cap = 0;
-        MQR_CHECK_HIP(hipMalloc(&S.buf, want));
-        S.cap = want;
-    }
+    if (grow(S.buf, off)) return 1;
     if (!S.h_sum) MQR_CHECK_HIP(hipHostMalloc(&S.h_sum, sizeof(PlanSummary), hipHostMallocDefault));
-    char* b = static_cast<char*>(S.buf);
+    char* b = S.buf.as<char>();
     auto U64 = [&](size_t o) { return reinterpret_cast<uint64_t*>(b + o); };
     auto I32 = [&](size_t o) { return reinterpret_cast<int32_t*>(b + o); };
     PlanSummary* dsum = reinterpret_cast<PlanSummary*>(b + o_sum);
@@ -559,17 +555,6 @@ static int device_plan(PlanScratch& S, hipStream_t st, const uint64_t* dkeys, in
     return 0;
 }
 
-static int grow(void** p, size_t* cap, size_t need) {
-    if (*cap >= need) return 0;
-    const size_t want = std::max(need, *cap + *cap / 2);  // 1.5x: few reallocations as counts vary
-    if (*p) MQR_CHECK_HIP(hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
-    MQR_CHECK_HIP(hipMalloc(p, want));
-    *cap = want;
-    return 0;
-}
-
 // Output volume of one rank: empty it, activate its keys in order (owned first).
 static int prepare_out(mqr_vbg* out, const uint64_t* dk, int64_t n, bool fused) {
     if (mqr_vbg_reset(out)) return 1;
@@ -589,26 +574,22 @@ struct Exchange {
     int W = 1, me = 0, R3 = 0;
     int pk = 0;                       // segment format (seg_load): 0 float2 pairs, 1 uint16 weights
     std::vector<size_t> soff, roff;  // block offsets of the segments
-    void* sendbuf = nullptr;
-    size_t send_cap = 0;
-    void* recvbuf = nullptr;
-    size_t recv_cap = 0;
-    void* csr = nullptr;  // fused merge: the [n_out][W] entry table
-    size_t csr_cap = 0;
+    GrowBuf sendbuf, recvbuf;
+    GrowBuf csr;  // fused merge: the [n_out][W] entry table
     bool fused = true;    // k_merge_fused (false: one k_merge_blocks launch per source, mqr_merge_set_per_source)
     Exchange() = default;
     Exchange(const Exchange&) = delete;
     Exchange& operator=(const Exchange&) = delete;
     ~Exchange() {
-        if (sendbuf) (void)hipFree(sendbuf);
-        if (recvbuf) (void)hipFree(recvbuf);
-        if (csr) (void)hipFree(csr);
+        if (sendbuf.p) (void)hipFree(sendbuf.p);
+        if (recvbuf.p) (void)hipFree(recvbuf.p);
+        if (csr.p) (void)hipFree(csr.p);
     }
     size_t send_blocks(int d) const { return soff[d + 1] - soff[d]; }
     size_t recv_blocks(int s) const { return roff[s + 1] - roff[s]; }
     size_t block_bytes() const { return seg_block_bytes(pk, R3); }
-    char* send_seg(int d) const { return static_cast<char*>(sendbuf) + soff[d] * block_bytes(); }
-    char* recv_seg(int s) const { return static_cast<char*>(recvbuf) + roff[s] * block_bytes(); }
+    char* send_seg(int d) const { return sendbuf.as<char>() + soff[d] * block_bytes(); }
+    char* recv_seg(int s) const { return recvbuf.as<char>() + roff[s] * block_bytes(); }
     size_t seg_bytes(size_t blocks) const { return blocks * block_bytes(); }
 };
 
@@ -646,17 +627,15 @@ static int xchg_prepare(Exchange& x, hipStream_t st, const uint64_t* dkeys, int 
     // (fused: the output's activation is not waited for -- the merge writes only pool buffers, and
     // activate_ordered_check reads its table-full flag after the merge)
     if (prepare_out(out, x.pv.out_keys, x.H.n_out, x.fused)) return 1;
-    if (grow(&x.sendbuf, &x.send_cap, std::max<size_t>(ns, 1) * eb) ||
-        grow(&x.recvbuf, &x.recv_cap, std::max<size_t>(nr, 1) * eb))
-        return 1;
+    if (grow(x.sendbuf, std::max<size_t>(ns, 1) * eb) || grow(x.recvbuf, std::max<size_t>(nr, 1) * eb)) return 1;
     if (order_after_volume_integrates(local, st)) return 1;
     if (ns) {
         if (x.pk)
             hipLaunchKernelGGL(k_gather_blocks<1>, dim3((unsigned)ns), dim3(256), 0, st, x.pv.send_idx, (int64_t)ns,
-                               local->pool, x.R3, static_cast<char*>(x.sendbuf));
+                               local->pool, x.R3, x.sendbuf.as<char>());
         else
             hipLaunchKernelGGL(k_gather_blocks<0>, dim3((unsigned)ns), dim3(256), 0, st, x.pv.send_idx, (int64_t)ns,
-                               local->pool, x.R3, static_cast<char*>(x.sendbuf));
+                               local->pool, x.R3, x.sendbuf.as<char>());
     }
     MQR_CHECK_HIP(hipGetLastError());
     if (ev_gathered) MQR_CHECK_HIP(hipEventRecord(ev_gathered, st));
@@ -687,8 +666,8 @@ static int xchg_merge(Exchange& x, hipStream_t st, mqr_vbg* out) {
         const int64_t n_out = x.H.n_out, nr = (int64_t)x.roff[x.W];
         if (n_out == 0) return 0;
         MQR_REQUIRE(x.W <= kMergeMaxEntries, "merge: too many ranks");
-        if (grow(&x.csr, &x.csr_cap, sizeof(int32_t) * (size_t)n_out * x.W)) return 1;
-        int32_t* ent = static_cast<int32_t*>(x.csr);
+        if (grow(x.csr, sizeof(int32_t) * (size_t)n_out * x.W)) return 1;
+        int32_t* ent = x.csr.as<int32_t>();
         MQR_CHECK_HIP(hipMemsetAsync(ent, 0xff, sizeof(int32_t) * (size_t)n_out * x.W, st));
         SegOffsets seg{};
         for (int r = 0; r <= x.W; ++r) seg.off[r] = (int64_t)x.roff[r];
@@ -698,7 +677,7 @@ static int xchg_merge(Exchange& x, hipStream_t st, mqr_vbg* out) {
         const int me = x.me;
         auto fused = x.pk ? k_merge_fused<1> : k_merge_fused<0>;
         hipLaunchKernelGGL(fused, dim3((unsigned)n_out), dim3(256), 0, st, ent, x.W, n_out,
-                           static_cast<const char*>(x.recvbuf), static_cast<const char*>(x.sendbuf),
+                           x.recvbuf.as<const char>(), x.sendbuf.as<const char>(),
                            (int64_t)x.roff[me], (int64_t)x.roff[me + 1], (int64_t)x.soff[me], x.R3, out->pool);
         MQR_CHECK_HIP(hipGetLastError());
         return 0;
@@ -801,7 +780,7 @@ int mqr_comm_destroy(mqr_comm* c) {
     RcclApi* api = rccl();
     if (api && c->nc) api->CommDestroy(c->nc);
     delete c->x;
-    if (c->small) (void)hipFree(c->small);
+    if (c->small.p) (void)hipFree(c->small.p);
     for (hipEvent_t e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->order) (void)hipEventDestroy(c->order);
@@ -857,8 +836,8 @@ int mqr_reduce_rccl(mqr_vbg* local, mqr_comm* c, int mode, int root, mqr_vbg* ou
     MQR_CHECK_HIP(hipEventRecord(c->ev[0], c->s));
     // 1. all-gather (block count, weight bound) pairs (host: the padding, the segment format), then the
     //    padded packed keys
-    if (grow(&c->small, &c->small_cap, sizeof(int64_t) * 2 * (W + 1))) return 1;
-    int64_t* dcnt = static_cast<int64_t*>(c->small);
+    if (grow(c->small, sizeof(int64_t) * 2 * (W + 1))) return 1;
+    int64_t* dcnt = c->small.as<int64_t>();
     MQR_CHECK_HIP(hipMemcpyAsync(dcnt + 2 * W, mine, sizeof(mine), hipMemcpyHostToDevice, c->s));
     MQR_CHECK_NCCL(api, api->AllGather(dcnt + 2 * W, dcnt, 2, ncclInt64, c->nc, c->s));
     MQR_CHECK_HIP(hipMemcpyAsync(cnt.data(), dcnt, sizeof(int64_t) * 2 * W, hipMemcpyDeviceToHost, c->s));
@@ -871,8 +850,8 @@ int mqr_reduce_rccl(mqr_vbg* local, mqr_comm* c, int mode, int root, mqr_vbg* ou
     }
     int64_t out_bound = -1;
     const int pk = seg_format(wb.data(), W, (int)local->R3, &out_bound);
-    if (grow(&c->small, &c->small_cap, sizeof(uint64_t) * mx * (W + 1))) return 1;
-    uint64_t* dkeys = static_cast<uint64_t*>(c->small);
+    if (grow(c->small, sizeof(uint64_t) * mx * (W + 1))) return 1;
+    uint64_t* dkeys = c->small.as<uint64_t>();
     uint64_t* dmine = dkeys + mx * W;
     MQR_CHECK_HIP(hipMemsetAsync(dmine, 0xff, sizeof(uint64_t) * mx, c->s));
     if (n_me)

@@ -31,6 +31,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 
 namespace mqr {
@@ -320,13 +321,12 @@ inline unsigned nb(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 2
 // Requests past the arena fall back to hipMallocAsync.  One call owns the cached arena at a time
 // (a concurrent call on another thread gets a private one).
 struct Arena {
-    char* base = nullptr;
-    size_t cap = 0;
+    GrowBuf buf;
     bool busy = false;
     hipStream_t s = nullptr;  // cached with the arena: creating a stream costs ~2 ms
 };
 static std::mutex g_arena_mu;
-static Arena g_arena[64];
+static Arena g_arena[kMaxDevices];
 
 struct Ctx {
     hipStream_t s = nullptr;
@@ -341,7 +341,7 @@ struct Ctx {
         device = dev;
         {
             std::lock_guard<std::mutex> lk(g_arena_mu);
-            if (dev >= 0 && dev < 64 && !g_arena[dev].busy) {
+            if (dev >= 0 && dev < kMaxDevices && !g_arena[dev].busy) {
                 ar = &g_arena[dev];
                 ar->busy = true;
             }
@@ -349,21 +349,14 @@ struct Ctx {
         if (!ar) ar = &priv;
         if (!ar->s && hipStreamCreateWithFlags(&ar->s, hipStreamNonBlocking) != hipSuccess) return 1;
         s = ar->s;
-        if (ar->cap < want) {
-            if (ar->base) (void)hipFree(ar->base);
-            ar->base = nullptr;
-            ar->cap = 0;
-            if (hipMalloc(&ar->base, want) != hipSuccess) return 1;
-            ar->cap = want;
-        }
-        return 0;
+        return ar->buf.reserve(want, want) != hipSuccess;
     }
     template <class T>
     T* alloc(int64_t n) {
-        const size_t bytes = (sizeof(T) * (size_t)std::max<int64_t>(n, 1) + 255) & ~(size_t)255;
-        if (ar && top + bytes <= ar->cap) {
+        const size_t bytes = al256(sizeof(T) * (size_t)std::max<int64_t>(n, 1));
+        if (ar && top + bytes <= ar->buf.cap) {
             stack.emplace_back(top, bytes);
-            void* p = ar->base + top;
+            void* p = ar->buf.as<char>() + top;
             top += bytes;
             return static_cast<T*>(p);
         }
@@ -373,8 +366,9 @@ struct Ctx {
         return static_cast<T*>(p);
     }
     void release(void* p) {
-        if (ar && p >= (void*)ar->base && p < (void*)(ar->base + ar->cap)) {
-            const size_t off = static_cast<char*>(p) - ar->base;
+        char* base = ar ? ar->buf.as<char>() : nullptr;
+        if (ar && p >= (void*)base && p < (void*)(base + ar->buf.cap)) {
+            const size_t off = static_cast<char*>(p) - base;
             for (size_t i = stack.size(); i-- > 0;)
                 if (stack[i].first == off) {
                     stack.erase(stack.begin() + (std::ptrdiff_t)i);
@@ -394,7 +388,7 @@ struct Ctx {
         for (void* p : owned) (void)hipFreeAsync(p, s);
         (void)hipStreamSynchronize(s);
         if (ar == &priv) {
-            if (priv.base) (void)hipFree(priv.base);
+            if (priv.buf.p) (void)hipFree(priv.buf.p);
             (void)hipStreamDestroy(priv.s);
         } else if (ar) {
             std::lock_guard<std::mutex> lk(g_arena_mu);
@@ -403,14 +397,6 @@ struct Ctx {
     }
 };
 
-#define MF_CHECK(expr)                                                           \
-    do {                                                                         \
-        hipError_t _e = (expr);                                                  \
-        if (_e != hipSuccess) {                                                  \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));        \
-            return 1;                                                            \
-        }                                                                        \
-    } while (0)
 #define MF_ALLOC(var, T, n)                                                      \
     T* var = c.alloc<T>(n);                                                      \
     if (!var) {                                                                  \
@@ -424,16 +410,16 @@ static int select_flagged(Ctx& c, const F* flags, int64_t n, int32_t* out, int64
     hipcub::CountingInputIterator<int32_t> it(0);
     int32_t* d_num = c.alloc<int32_t>(1);
     size_t tb = 0;
-    MF_CHECK(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flags, out, d_num, (int)n, c.s));
+    MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flags, out, d_num, (int)n, c.s));
     void* tmp = c.alloc<char>((int64_t)tb + 16);
     if (!d_num || !tmp) {
         set_error("mesh filter: device allocation failed");
         return 1;
     }
-    MF_CHECK(hipcub::DeviceSelect::Flagged(tmp, tb, it, flags, out, d_num, (int)n, c.s));
+    MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(tmp, tb, it, flags, out, d_num, (int)n, c.s));
     int32_t h = 0;
-    MF_CHECK(hipMemcpyAsync(&h, d_num, sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
-    MF_CHECK(hipStreamSynchronize(c.s));
+    MQR_CHECK_HIP(hipMemcpyAsync(&h, d_num, sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
+    MQR_CHECK_HIP(hipStreamSynchronize(c.s));
     c.release(tmp);
     c.release(d_num);
     *count = h;
@@ -442,13 +428,13 @@ static int select_flagged(Ctx& c, const F* flags, int64_t n, int32_t* out, int64
 
 static int exclusive_sum(Ctx& c, const int32_t* in, int32_t* out, int64_t n) {
     size_t tb = 0;
-    MF_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, c.s));
+    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, c.s));
     void* tmp = c.alloc<char>((int64_t)tb + 16);
     if (!tmp) {
         set_error("mesh filter: device allocation failed");
         return 1;
     }
-    MF_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, c.s));
+    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, c.s));
     c.release(tmp);  // stream-ordered reuse: later work on c.s runs after the scan
     return 0;
 }
@@ -456,13 +442,13 @@ static int exclusive_sum(Ctx& c, const int32_t* in, int32_t* out, int64_t n) {
 template <class K>
 static int sort_pairs(Ctx& c, const K* kin, K* kout, const int32_t* vin, int32_t* vout, int64_t n, int bits) {
     size_t tb = 0;
-    MF_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, bits, c.s));
+    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, bits, c.s));
     void* tmp = c.alloc<char>((int64_t)tb + 16);
     if (!tmp) {
         set_error("mesh filter: device allocation failed");
         return 1;
     }
-    MF_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, vin, vout, (int)n, 0, bits, c.s));
+    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, vin, vout, (int)n, 0, bits, c.s));
     c.release(tmp);
     return 0;
 }
@@ -485,7 +471,7 @@ static int keep_triangles(Ctx& c, Mesh& m, const uint8_t* keep) {
     }
     MF_ALLOC(tri2, int32_t, 3 * k);
     if (k) hipLaunchKernelGGL(k_gather_tris, dim3(nb(k)), dim3(256), 0, c.s, m.tri, sel, k, tri2);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     c.release(sel);
     c.release(m.tri);
     m.tri = tri2;
@@ -499,7 +485,7 @@ static int keep_vertices(Ctx& c, Mesh& m, const int32_t* keepv, const int32_t* m
     int64_t k = 0;
     if (select_flagged(c, keepv, m.nv, sel, &k)) return 1;
     if (m.nt) hipLaunchKernelGGL(k_remap, dim3(nb(3 * m.nt)), dim3(256), 0, c.s, m.tri, m.nt, map);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (k != m.nv) {
         MF_ALLOC(pos2, float, 3 * k);
         float* nrm2 = nullptr;
@@ -511,7 +497,7 @@ static int keep_vertices(Ctx& c, Mesh& m, const int32_t* keepv, const int32_t* m
             }
         }
         if (k) hipLaunchKernelGGL(k_gather_vertices, dim3(nb(k)), dim3(256), 0, c.s, m.pos, m.nrm, sel, k, pos2, nrm2);
-        MF_CHECK(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         c.release(m.pos);
         if (m.nrm) c.release(m.nrm);
         m.pos = pos2;
@@ -525,9 +511,9 @@ static int keep_vertices(Ctx& c, Mesh& m, const int32_t* keepv, const int32_t* m
 static int remove_unreferenced_vertices(Ctx& c, Mesh& m) {
     MF_ALLOC(used, int32_t, m.nv);
     MF_ALLOC(newidx, int32_t, m.nv);
-    MF_CHECK(hipMemsetAsync(used, 0, sizeof(int32_t) * m.nv, c.s));
+    MQR_CHECK_HIP(hipMemsetAsync(used, 0, sizeof(int32_t) * m.nv, c.s));
     if (m.nt) hipLaunchKernelGGL(k_mark_vertices, dim3(nb(3 * m.nt)), dim3(256), 0, c.s, m.tri, m.nt, used);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (exclusive_sum(c, used, newidx, m.nv)) return 1;
     if (keep_vertices(c, m, used, newidx)) return 1;
     c.release(used);
@@ -547,13 +533,13 @@ static int remove_duplicated_triangles(Ctx& c, Mesh& m) {
     MF_ALLOC(idx2, int32_t, n);
     MF_ALLOC(keep, uint8_t, n);
     hipLaunchKernelGGL(k_tri_key_lo, dim3(nb(n)), dim3(256), 0, c.s, m.tri, n, k2, idx);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (sort_pairs(c, k2, k2s, idx, idx1, n, 32)) return 1;
     hipLaunchKernelGGL(k_tri_key_hi, dim3(nb(n)), dim3(256), 0, c.s, m.tri, idx1, n, k01);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (sort_pairs(c, k01, k01s, idx1, idx2, n, 64)) return 1;
     hipLaunchKernelGGL(k_first_of_run_tri, dim3(nb(n)), dim3(256), 0, c.s, m.tri, idx2, n, keep);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (keep_triangles(c, m, keep)) return 1;
     for (void* p : {(void*)k2, (void*)k2s, (void*)idx, (void*)idx1, (void*)k01, (void*)k01s, (void*)idx2, (void*)keep})
         c.release(p);
@@ -581,30 +567,30 @@ static int remove_duplicated_vertices(Ctx& c, Mesh& m) {
     MF_ALLOC(newidx, int32_t, n);
     MF_ALLOC(map, int32_t, n);
     hipLaunchKernelGGL(k_vtx_key_lo, dim3(nb(n)), dim3(256), 0, c.s, m.pos, n, kz, idx);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (sort_pairs(c, kz, kzs, idx, idx1, n, 32)) return 1;
     hipLaunchKernelGGL(k_vtx_key_hi, dim3(nb(n)), dim3(256), 0, c.s, m.pos, idx1, n, kxy);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (sort_pairs(c, kxy, kxys, idx1, idx2, n, 64)) return 1;
     hipLaunchKernelGGL(k_vtx_heads, dim3(nb(n)), dim3(256), 0, c.s, m.pos, idx2, n, head);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     {
         size_t tb = 0;
-        MF_CHECK(hipcub::DeviceScan::InclusiveScan(nullptr, tb, head, start, MaxOp(), (int)n, c.s));
+        MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb, head, start, MaxOp(), (int)n, c.s));
         void* tmp = c.alloc<char>((int64_t)tb + 16);
         if (!tmp) {
             set_error("mesh filter: device allocation failed");
             return 1;
         }
-        MF_CHECK(hipcub::DeviceScan::InclusiveScan(tmp, tb, head, start, MaxOp(), (int)n, c.s));
-        MF_CHECK(hipStreamSynchronize(c.s));
+        MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveScan(tmp, tb, head, start, MaxOp(), (int)n, c.s));
+        MQR_CHECK_HIP(hipStreamSynchronize(c.s));
         c.release(tmp);
     }
     hipLaunchKernelGGL(k_vtx_rep, dim3(nb(n)), dim3(256), 0, c.s, idx2, start, n, rep, keepv);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (exclusive_sum(c, keepv, newidx, n)) return 1;
     hipLaunchKernelGGL(k_vtx_map, dim3(nb(n)), dim3(256), 0, c.s, rep, newidx, n, map);
-    MF_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     if (keep_vertices(c, m, keepv, map)) return 1;
     for (void* p : {(void*)kz, (void*)kzs, (void*)idx, (void*)idx1, (void*)kxy, (void*)kxys, (void*)idx2, (void*)head,
                     (void*)start, (void*)rep, (void*)keepv, (void*)newidx, (void*)map})
@@ -623,7 +609,7 @@ static int remove_non_manifold_edges(Ctx& c, Mesh& m, int64_t* removed) {
         if (n == 0) break;
         MF_ALLOC(area, double, n);
         hipLaunchKernelGGL(k_areas, dim3(nb(n)), dim3(256), 0, c.s, m.pos, m.tri, n, area);
-        MF_CHECK(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         const int64_t ne = 3 * n;
         MF_ALLOC(keys, uint64_t, ne);
         MF_ALLOC(keys_s, uint64_t, ne);
@@ -632,10 +618,10 @@ static int remove_non_manifold_edges(Ctx& c, Mesh& m, int64_t* removed) {
         MF_ALLOC(flag, uint8_t, ne);
         MF_ALLOC(mem, int32_t, ne);
         hipLaunchKernelGGL(k_edge_keys, dim3(nb(ne)), dim3(256), 0, c.s, m.tri, n, keys, slot);
-        MF_CHECK(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         if (sort_pairs(c, keys, keys_s, slot, slot_s, ne, 64)) return 1;
         hipLaunchKernelGGL(k_nonmanifold_members, dim3(nb(ne)), dim3(256), 0, c.s, keys_s, ne, flag);
-        MF_CHECK(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         int64_t nm = 0;
         if (select_flagged(c, flag, ne, mem, &nm)) return 1;
         const bool manifold = nm == 0;
@@ -645,14 +631,14 @@ static int remove_non_manifold_edges(Ctx& c, Mesh& m, int64_t* removed) {
             MF_ALLOC(marea, double, nm);
             hipLaunchKernelGGL(k_gather_members, dim3(nb(nm)), dim3(256), 0, c.s, keys_s, slot_s, area, mem, nm, mkey,
                                mtri, marea);
-            MF_CHECK(hipGetLastError());
+            MQR_CHECK_HIP(hipGetLastError());
             std::vector<uint64_t> hk(nm);
             std::vector<int32_t> ht(nm);
             std::vector<double> ha(nm);
-            MF_CHECK(hipMemcpyAsync(hk.data(), mkey, sizeof(uint64_t) * nm, hipMemcpyDeviceToHost, c.s));
-            MF_CHECK(hipMemcpyAsync(ht.data(), mtri, sizeof(int32_t) * nm, hipMemcpyDeviceToHost, c.s));
-            MF_CHECK(hipMemcpyAsync(ha.data(), marea, sizeof(double) * nm, hipMemcpyDeviceToHost, c.s));
-            MF_CHECK(hipStreamSynchronize(c.s));
+            MQR_CHECK_HIP(hipMemcpyAsync(hk.data(), mkey, sizeof(uint64_t) * nm, hipMemcpyDeviceToHost, c.s));
+            MQR_CHECK_HIP(hipMemcpyAsync(ht.data(), mtri, sizeof(int32_t) * nm, hipMemcpyDeviceToHost, c.s));
+            MQR_CHECK_HIP(hipMemcpyAsync(ha.data(), marea, sizeof(double) * nm, hipMemcpyDeviceToHost, c.s));
+            MQR_CHECK_HIP(hipStreamSynchronize(c.s));
             std::unordered_map<int32_t, double> cur;  // current area of every triangle involved
             cur.reserve((size_t)nm);
             for (int64_t j = 0; j < nm; ++j) cur.emplace(ht[j], ha[j]);
@@ -676,11 +662,12 @@ static int remove_non_manifold_edges(Ctx& c, Mesh& m, int64_t* removed) {
             }
             if (!del.empty()) {
                 MF_ALLOC(ddel, int32_t, (int64_t)del.size());
-                MF_CHECK(hipMemcpyAsync(ddel, del.data(), sizeof(int32_t) * del.size(), hipMemcpyHostToDevice, c.s));
+                MQR_CHECK_HIP(hipMemcpyAsync(ddel, del.data(), sizeof(int32_t) * del.size(),
+                                             hipMemcpyHostToDevice, c.s));
                 hipLaunchKernelGGL(k_drop_tris, dim3(nb((int64_t)del.size())), dim3(256), 0, c.s, ddel,
                                    (int64_t)del.size(), area);
-                MF_CHECK(hipGetLastError());
-                MF_CHECK(hipStreamSynchronize(c.s));  // `del` is pageable host memory
+                MQR_CHECK_HIP(hipGetLastError());
+                MQR_CHECK_HIP(hipStreamSynchronize(c.s));  // `del` is pageable host memory
                 c.release(ddel);
             }
             c.release(marea);
@@ -689,7 +676,7 @@ static int remove_non_manifold_edges(Ctx& c, Mesh& m, int64_t* removed) {
         }
         MF_ALLOC(keep, uint8_t, n);
         hipLaunchKernelGGL(k_keep_positive, dim3(nb(n)), dim3(256), 0, c.s, area, n, keep);
-        MF_CHECK(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         if (keep_triangles(c, m, keep)) return 1;
         for (void* p : {(void*)area, (void*)keys, (void*)keys_s, (void*)slot, (void*)slot_s, (void*)flag, (void*)mem,
                         (void*)keep})
@@ -829,22 +816,16 @@ int mqr_mesh_filter_components(int device, const float* vertices, const float* n
     g->device = device;
     g->nv = m.nv;
     g->nt = m.nt;
-    const size_t sv = (sizeof(float) * 3 * (size_t)std::max<int64_t>(m.nv, 1) + 255) & ~(size_t)255;
-    const size_t stb = (sizeof(int32_t) * 3 * (size_t)std::max<int64_t>(m.nt, 1) + 255) & ~(size_t)255;
-    g->blk = geom_block_alloc(device, 2 * sv + stb, &g->blk_cap);
-    if (!g->blk) {
+    if (geom_alloc(g, m.nv, m.nt)) {
         delete g;
         set_error("mesh filter: device allocation failed");
         return 1;
     }
-    g->pos = reinterpret_cast<float*>(g->blk);
-    g->nrm = reinterpret_cast<float*>(static_cast<char*>(g->blk) + sv);
-    g->tri = reinterpret_cast<int32_t*>(static_cast<char*>(g->blk) + 2 * sv);
     if (m.nv) MQR_CHECK_HIP(hipMemcpyAsync(g->pos, m.pos, sizeof(float) * 3 * m.nv, hipMemcpyDeviceToDevice, c.s));
     if (m.nv && m.nrm)
         MQR_CHECK_HIP(hipMemcpyAsync(g->nrm, m.nrm, sizeof(float) * 3 * m.nv, hipMemcpyDeviceToDevice, c.s));
-    else
-        MQR_CHECK_HIP(hipMemsetAsync(g->nrm, 0, sv, c.s));
+    else  // zeros over the normals' whole piece of the block (it ends where the triangles begin)
+        MQR_CHECK_HIP(hipMemsetAsync(g->nrm, 0, (char*)g->tri - (char*)g->nrm, c.s));
     if (m.nt) MQR_CHECK_HIP(hipMemcpyAsync(g->tri, m.tri, sizeof(int32_t) * 3 * m.nt, hipMemcpyDeviceToDevice, c.s));
     MQR_CHECK_HIP(hipStreamSynchronize(c.s));
     *out = g;

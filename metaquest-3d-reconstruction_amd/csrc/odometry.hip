@@ -24,6 +24,7 @@
 #include <mutex>
 #include <vector>
 
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 #include "pair_reduce.hpp"
 
@@ -36,7 +37,6 @@ using pairsum::kWaves;
 constexpr int kPix = 4;                   // pixels per lane
 constexpr int kTile = kThreads * kPix;    // pixels per workgroup
 constexpr int kMaxPairs = 65535;          // grid.y
-constexpr int kDevices = 16;
 
 struct Pair {
     double T[12];  // source camera -> target camera, rows of [R | t]
@@ -103,30 +103,18 @@ __global__ __launch_bounds__(64) void k_odometry_finalize(const double* __restri
     if (threadIdx.x == 0) counts[pair] = (int64_t)S[0];
 }
 
-// grow-only device scratch per device, kept between calls for the life of the process: 0 host frames (a
-// copy of the whole stack), 1 pairs, 2 slabs, 3 outputs.  A buffer is regrown through hipFree, which waits
-// for the device, so work a failed call left queued has finished with it.
+// grow-only device scratch per device (GrowBuf), kept between calls for the life of the process: 0 host
+// frames (a copy of the whole stack), 1 pairs, 2 slabs, 3 outputs
 struct Cache {
     std::mutex mu;
-    void* buf[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap[4] = {0, 0, 0, 0};
+    GrowBuf buf[4];
 
-    void* get(int slot, size_t bytes) {
-        if (cap[slot] < bytes) {
-            if (buf[slot]) (void)hipFree(buf[slot]);
-            buf[slot] = nullptr;
-            cap[slot] = 0;
-            const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-            if (hipMalloc(&buf[slot], want) != hipSuccess) {
-                (void)hipGetLastError();
-                return nullptr;
-            }
-            cap[slot] = want;
-        }
-        return buf[slot];
+    void* get(int slot, size_t bytes) {  // nullptr when the device is out of memory
+        (void)buf[slot].reserve(bytes, std::max<size_t>(bytes + bytes / 2, 4096));
+        return buf[slot].p;
     }
 };
-Cache g_cache[kDevices];
+Cache g_cache[kMaxDevices];
 
 }  // namespace odo
 }  // namespace mqr
@@ -143,7 +131,7 @@ extern "C" int mqr_odometry_information_pairs(int device, const float* depths, i
     MQR_REQUIRE(depths && K && src && tgt && T && info, "null argument");
     MQR_REQUIRE(depth_loc == MQR_HOST || depth_loc == MQR_DEVICE, "depth_loc must be MQR_HOST or MQR_DEVICE");
     MQR_REQUIRE(N > 0 && H > 0 && W > 0, "bad shape");
-    MQR_REQUIRE(device >= 0 && device < kDevices, "bad device");
+    MQR_REQUIRE(device >= 0 && device < kMaxDevices, "bad device");
     const int64_t HW = (int64_t)H * W;
     MQR_REQUIRE(HW < ((int64_t)1 << 31), "frame too large");
     for (int a = 0; a < 9; ++a) MQR_REQUIRE(std::isfinite(K[a]), "non-finite intrinsic matrix");

@@ -418,9 +418,6 @@ static void free_built(mqr_scene* s) {
     s->built = false;
 }
 
-static size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
-
 static int build(mqr_scene* s) {
     if (s->built) return 0;
     free_built(s);

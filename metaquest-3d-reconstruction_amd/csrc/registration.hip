@@ -29,6 +29,7 @@
 #include <tuple>
 #include <vector>
 
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 #include "pair_reduce.hpp"
 
@@ -336,15 +337,6 @@ __global__ __launch_bounds__(64) void k_finalize_info(const PairDesc* __restrict
 // ------------------------------------------------------------------ host side
 inline unsigned nb(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
 
-#define RG_CHECK(expr)                                                           \
-    do {                                                                         \
-        hipError_t _e = (expr);                                                  \
-        if (_e != hipSuccess) {                                                  \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));        \
-            return 1;                                                            \
-        }                                                                        \
-    } while (0)
-
 struct Selection {  // points of one (cloud, kind, parameter)
     const float* pts = nullptr;
     int64_t n = 0;
@@ -381,19 +373,11 @@ struct mqr_cloudset {
     std::map<GridKey, Grid> grids;
     int* d_flag = nullptr;
     // grow-only scratch of the pair calls: 0 descriptors, 1 state, 2 slabs, 3 information
-    void* scratch[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t scratch_cap[4] = {0, 0, 0, 0};
+    GrowBuf scratch[4];
 
-    void* get_scratch(int slot, size_t bytes) {
-        if (scratch_cap[slot] < bytes) {
-            if (scratch[slot]) (void)hipFree(scratch[slot]);
-            scratch[slot] = nullptr;
-            scratch_cap[slot] = 0;
-            const size_t want = std::max<size_t>(bytes + bytes / 2, 4096);
-            if (hipMalloc(&scratch[slot], want) != hipSuccess) return nullptr;
-            scratch_cap[slot] = want;
-        }
-        return scratch[slot];
+    void* get_scratch(int slot, size_t bytes) {  // nullptr when the device is out of memory
+        (void)scratch[slot].reserve(bytes, std::max<size_t>(bytes + bytes / 2, 4096));
+        return scratch[slot].p;
     }
 };
 
@@ -417,19 +401,19 @@ int sorted_keys(mqr_cloudset* cs, const float* pts, int64_t n, double e, uint64_
         set_error("registration: device allocation failed");
         return 1;
     }
-    RG_CHECK(hipMemsetAsync(cs->d_flag, 0, sizeof(int), cs->s));
+    MQR_CHECK_HIP(hipMemsetAsync(cs->d_flag, 0, sizeof(int), cs->s));
     hipLaunchKernelGGL(k_cell_keys, dim3(nb(n)), dim3(256), 0, cs->s, pts, n, e, keys.p, idx.p, cs->d_flag);
-    RG_CHECK(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     size_t tb = 0;
-    RG_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, keys_s, idx.p, idx_s, (int)n, 0, 63, cs->s));
+    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, keys_s, idx.p, idx_s, (int)n, 0, 63, cs->s));
     if (tmp.alloc((int64_t)tb + 16)) {
         set_error("registration: device allocation failed");
         return 1;
     }
-    RG_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.p, keys_s, idx.p, idx_s, (int)n, 0, 63, cs->s));
+    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.p, keys_s, idx.p, idx_s, (int)n, 0, 63, cs->s));
     int flag = 0;
-    RG_CHECK(hipMemcpyAsync(&flag, cs->d_flag, sizeof(int), hipMemcpyDeviceToHost, cs->s));
-    RG_CHECK(hipStreamSynchronize(cs->s));
+    MQR_CHECK_HIP(hipMemcpyAsync(&flag, cs->d_flag, sizeof(int), hipMemcpyDeviceToHost, cs->s));
+    MQR_CHECK_HIP(hipStreamSynchronize(cs->s));
     if (flag) {
         set_error("registration: a coordinate divided by the cell size " + std::to_string(e) +
                   " gives a cell index beyond 2^20, which the 63-bit key cannot hold");
@@ -456,9 +440,9 @@ int get_selection(mqr_cloudset* cs, int cloud, int kind, double param, const Sel
         sel.n = n;
     } else if (kind == kEveryK) {
         const int64_t k = (int64_t)param, m = (n + k - 1) / k;
-        RG_CHECK(hipMalloc(&sel.owned, sizeof(float) * 3 * (size_t)m));
+        MQR_CHECK_HIP(hipMalloc(&sel.owned, sizeof(float) * 3 * (size_t)m));
         hipLaunchKernelGGL(k_every_k, dim3(nb(m)), dim3(256), 0, cs->s, src, m, k, sel.owned);
-        RG_CHECK(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         sel.pts = sel.owned;
         sel.n = m;
     } else {
@@ -472,27 +456,27 @@ int get_selection(mqr_cloudset* cs, int cloud, int kind, double param, const Sel
         }
         if (int rc = sorted_keys(cs, src, n, param, keys_s.p, idx_s.p)) return rc;
         hipLaunchKernelGGL(k_heads, dim3(nb(n)), dim3(256), 0, cs->s, keys_s.p, n, head.p);
-        RG_CHECK(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         hipcub::CountingInputIterator<int32_t> iota(0);
         size_t tb = 0;
-        RG_CHECK(hipcub::DeviceSelect::Flagged(nullptr, tb, iota, head.p, start.p, d_num.p, (int)n, cs->s));
+        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, iota, head.p, start.p, d_num.p, (int)n, cs->s));
         if (tmp.alloc((int64_t)tb + 16)) {
             set_error("registration: device allocation failed");
             return 1;
         }
-        RG_CHECK(hipcub::DeviceSelect::Flagged(tmp.p, tb, iota, head.p, start.p, d_num.p, (int)n, cs->s));
+        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(tmp.p, tb, iota, head.p, start.p, d_num.p, (int)n, cs->s));
         int32_t m = 0;
-        RG_CHECK(hipMemcpyAsync(&m, d_num.p, sizeof(int32_t), hipMemcpyDeviceToHost, cs->s));
-        RG_CHECK(hipStreamSynchronize(cs->s));
+        MQR_CHECK_HIP(hipMemcpyAsync(&m, d_num.p, sizeof(int32_t), hipMemcpyDeviceToHost, cs->s));
+        MQR_CHECK_HIP(hipStreamSynchronize(cs->s));
         if (m < 1 || m > n) {
             set_error("registration: voxel count out of range");
             return 1;
         }
-        RG_CHECK(hipMalloc(&sel.owned, sizeof(float) * 3 * (size_t)m));
+        MQR_CHECK_HIP(hipMalloc(&sel.owned, sizeof(float) * 3 * (size_t)m));
         hipLaunchKernelGGL(k_voxel_mean, dim3(nb(m)), dim3(256), 0, cs->s, src, idx_s.p, start.p, (int64_t)m, n,
                            sel.owned);
-        RG_CHECK(hipGetLastError());
-        RG_CHECK(hipStreamSynchronize(cs->s));  // the temporaries go out of scope
+        MQR_CHECK_HIP(hipGetLastError());
+        MQR_CHECK_HIP(hipStreamSynchronize(cs->s));  // the temporaries go out of scope
         sel.pts = sel.owned;
         sel.n = m;
     }
@@ -517,9 +501,9 @@ int get_grid(mqr_cloudset* cs, int cloud, int kind, double param, double cell, c
     }
     Grid g;
     const int64_t n = sel->n;
-    RG_CHECK(hipMalloc(&g.keys, sizeof(uint64_t) * (size_t)n));
-    RG_CHECK(hipMalloc(&g.order, sizeof(int32_t) * (size_t)n));
-    RG_CHECK(hipMalloc(&g.pts, sizeof(float) * 3 * (size_t)n));
+    MQR_CHECK_HIP(hipMalloc(&g.keys, sizeof(uint64_t) * (size_t)n));
+    MQR_CHECK_HIP(hipMalloc(&g.order, sizeof(int32_t) * (size_t)n));
+    MQR_CHECK_HIP(hipMalloc(&g.pts, sizeof(float) * 3 * (size_t)n));
     int rc = sorted_keys(cs, sel->pts, n, cell, g.keys, g.order);
     if (!rc) {
         hipLaunchKernelGGL(k_gather_points, dim3(nb(n)), dim3(256), 0, cs->s, sel->pts, g.order, n, g.pts);
@@ -578,8 +562,9 @@ int make_batch(mqr_cloudset* cs, int n_pairs, const int32_t* src, const int32_t*
         set_error("registration: device allocation failed");
         return 1;
     }
-    RG_CHECK(hipMemcpyAsync(b->d_desc, h.data(), sizeof(PairDesc) * (size_t)n_pairs, hipMemcpyHostToDevice, cs->s));
-    RG_CHECK(hipStreamSynchronize(cs->s));  // `h` is pageable host memory
+    MQR_CHECK_HIP(hipMemcpyAsync(b->d_desc, h.data(), sizeof(PairDesc) * (size_t)n_pairs,
+                                 hipMemcpyHostToDevice, cs->s));
+    MQR_CHECK_HIP(hipStreamSynchronize(cs->s));  // `h` is pageable host memory
     return 0;
 }
 
@@ -603,15 +588,17 @@ int upload_state(mqr_cloudset* cs, int n_pairs, const double* T, PairState** d_s
     }
     *d_state = static_cast<PairState*>(cs->get_scratch(1, sizeof(PairState) * (size_t)n_pairs));
     MQR_REQUIRE(*d_state, "registration: device allocation failed");
-    RG_CHECK(hipMemcpyAsync(*d_state, h.data(), sizeof(PairState) * (size_t)n_pairs, hipMemcpyHostToDevice, cs->s));
-    RG_CHECK(hipStreamSynchronize(cs->s));
+    MQR_CHECK_HIP(hipMemcpyAsync(*d_state, h.data(), sizeof(PairState) * (size_t)n_pairs,
+                                 hipMemcpyHostToDevice, cs->s));
+    MQR_CHECK_HIP(hipStreamSynchronize(cs->s));
     return 0;
 }
 
 int download_state(mqr_cloudset* cs, int n_pairs, const PairState* d_state, std::vector<PairState>* h) {
     h->resize((size_t)n_pairs);
-    RG_CHECK(hipMemcpyAsync(h->data(), d_state, sizeof(PairState) * (size_t)n_pairs, hipMemcpyDeviceToHost, cs->s));
-    RG_CHECK(hipStreamSynchronize(cs->s));
+    MQR_CHECK_HIP(hipMemcpyAsync(h->data(), d_state, sizeof(PairState) * (size_t)n_pairs,
+                                 hipMemcpyDeviceToHost, cs->s));
+    MQR_CHECK_HIP(hipStreamSynchronize(cs->s));
     return 0;
 }
 
@@ -694,8 +681,8 @@ int mqr_cloudset_destroy(mqr_cloudset* cs) {
         (void)hipFree(kv.second.pts);
     }
     for (void* p : cs->owned) (void)hipFree(p);
-    for (void* p : cs->scratch)
-        if (p) (void)hipFree(p);
+    for (GrowBuf& b : cs->scratch)
+        if (b.p) (void)hipFree(b.p);
     if (cs->d_flag) (void)hipFree(cs->d_flag);
     if (cs->s) (void)hipStreamDestroy(cs->s);
     delete cs;

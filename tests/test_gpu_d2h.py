@@ -1,5 +1,5 @@
 """Large host <-> device copies.  Downloads into pageable memory from 32 MiB on go through
-csrc/extract.hip ring_copy (copy kernels into a ring of pinned slots, host threads copying them out),
+csrc/devmem.hip ring_copy (copy kernels into a ring of pinned slots, host threads copying them out),
 used by mqr_memcpy, mqr_geom_copy and the host-array outputs of colouring, ray casting, confidence and
 decoding; uploads use HIP's pageable path.  Byte-exact against torch's own copy for: more chunks than
 ring slots, lengths that are not a multiple of the chunk or of 16 bytes, sources / destinations that are

@@ -412,6 +412,40 @@ int mqr_mesh_filter_components(int device, const float* vertices, const float* n
                                const int32_t* triangles, int64_t nt, int loc, int64_t min_triangle_count,
                                mqr_geom** out, int64_t* stats);
 
+/* compute_raw_metrics_for_mesh (scripts/evaluation/evaluate_fbx_quality.py:253-441) on the device: the
+ * reference's raw quality metrics of one triangle mesh -- triangle shape, edge topology, vertex-graph
+ * components, vertex-normal deviation and dihedral statistics, the 10^3 vertex-density grid and the
+ * colour gradient -- in float64 on float32 inputs.  The fields are RawMeshMetrics' after name / path,
+ * in its order; booleans are 0 / 1.  vertices nv*3 float32, colors nullable nv*3 float32 in [0, 1],
+ * triangles nt*3 int32, all in `loc` memory (MQR_DEVICE buffers are read in place).  Errors: nv == 0
+ * or nt == 0 (the reference raises ValueError), 3 nt >= 2^31, a non-finite coordinate, a triangle
+ * index outside [0, nv) (found by a kernel that reads only the indices, before any gather). */
+typedef struct mqr_quality_metrics {
+    double mean_aspect_ratio;
+    double mean_skewness;
+    int64_t degenerate_triangles;
+    int64_t non_manifold_edges;
+    double boundary_edge_ratio;
+    int64_t component_count;
+    int64_t total_edges;
+    double normal_deviation_avg_deg;
+    double dihedral_min_deg;
+    double dihedral_max_deg;
+    double dihedral_penalty;
+    double surface_roughness;
+    int64_t is_single_component;
+    double vertex_density_stddev;
+    int64_t has_color;
+    double uncolored_vertex_ratio;
+    double color_gradient_stddev;
+    int64_t is_manifold;
+    int64_t is_watertight;
+    int64_t num_vertices;
+    int64_t num_triangles;
+} mqr_quality_metrics;
+int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float* colors, const int32_t* triangles,
+                     int64_t nt, int loc, mqr_quality_metrics* out);
+
 /* Fragment registration (refine_fragment_poses.py:122-271): a CLOUD SET of N float32 xyz clouds in
  * HBM and three batched operations over pairs of them, standing in for Open3D's
  * evaluate_registration, multi_scale_icp (point to point) and get_information_matrix.

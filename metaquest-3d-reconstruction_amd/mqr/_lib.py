@@ -135,6 +135,8 @@ SIGNATURES = {
                                            ctypes.c_int]),
     "mqr_mesh_filter_components": (ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64,
                                                   ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_vp), _i64p]),
+    "mqr_mesh_quality": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, ctypes.c_int,
+                                        _vp]),
     "mqr_vbg_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_vbg_set_variant": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_check_div64": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
@@ -264,7 +266,7 @@ ORDERED = frozenset({
     "mqr_xchg_recv_segment", "mqr_geom_copy", "mqr_confidence", "mqr_confidence_counts", "mqr_decode_depth", "mqr_decode_depth_masked",
     "mqr_color_vertices",
     "mqr_color_map", "mqr_scene_add_triangles", "mqr_scene_cast_pinhole", "mqr_scene_cast_rays",
-    "mqr_mesh_filter_components", "mqr_memcpy",
+    "mqr_mesh_filter_components", "mqr_mesh_quality", "mqr_memcpy",
     "mqr_cloudset_create", "mqr_cloudset_voxel_down", "mqr_evaluate_pairs", "mqr_icp_pairs", "mqr_information_pairs",
     "mqr_odometry_information_pairs", "mqr_colormap_create", "mqr_colormap_colors",
 })

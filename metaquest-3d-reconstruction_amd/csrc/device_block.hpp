@@ -2,12 +2,13 @@
 // process's device-block cache (geom_block_alloc / geom_block_release): one block carved into 256-byte
 // aligned pieces and returned to the cache at scope exit, instead of a hipMalloc / hipFree pair per array
 // per call (hipFree synchronises the device; fresh allocations map pages).  The owner synchronises its
-// stream before the scope ends.  Also the grow-only buffer every module keeps between calls (GrowBuf) and
-// the carve of a geometry result (geom_alloc).
+// stream before the scope ends.  Also the grow-only buffer every module keeps between calls (GrowBuf), the
+// per-device stream table (StreamTable) and the carve of a geometry result (geom_alloc).
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
+#include <mutex>
 
 #include "mqr_common.hpp"
 
@@ -45,6 +46,23 @@ struct GrowBuf {
     hipError_t reserve(size_t need, size_t alloc_bytes);
     template <class T>
     T* as() const { return static_cast<T*>(p); }
+};
+
+// One non-blocking stream per device, created on first use and kept (creating a stream costs ~2 ms).  Each
+// module keeps a table of its own, so modules run beside each other.  get(): nullptr for a device outside
+// the table, or when the stream cannot be created (the sticky error is cleared).
+struct StreamTable {
+    std::mutex mu;
+    hipStream_t s[kMaxDevices] = {};
+    hipStream_t get(int device) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (device < 0 || device >= kMaxDevices) return nullptr;
+        if (!s[device] && hipStreamCreateWithFlags(&s[device], hipStreamNonBlocking) != hipSuccess) {
+            (void)hipGetLastError();
+            s[device] = nullptr;
+        }
+        return s[device];
+    }
 };
 
 // One cached block for the positions, normals and triangles of a geometry result, recycled across results

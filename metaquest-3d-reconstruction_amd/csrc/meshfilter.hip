@@ -17,68 +17,35 @@
 // ascending (v_min, v_max) order (the result differs only where two non-manifold edges share a
 // triangle).
 //
-// Device work: edge keys (u64) -> hipcub radix sort -> union-find over triangles (hook larger
-// root under smaller, so the root is the component's lowest triangle index) -> per-cluster
-// counts; stable compactions with hipcub::DeviceSelect; duplicate detection by two stable radix
-// passes over the canonical keys.  Only the short list of non-manifold edges goes to the host.
+// Device work: the sorted edge list and the union-find of mesh_edges.hpp, over triangles (the root
+// is the component's lowest triangle index) -> per-cluster counts; stable compactions with
+// hipcub::DeviceSelect; duplicate detection by two stable radix passes over the canonical keys.
+// Only the short list of non-manifold edges goes to the host.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <limits>
-#include <map>
+#include <memory>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
 
 #include "device_block.hpp"
+#include "mesh_edges.hpp"
 #include "mqr_common.hpp"
 
 namespace mqr {
 namespace mf {
+using namespace edges;
 
 // ------------------------------------------------------------------ kernels
-__global__ void k_iota(int32_t* a, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = (int32_t)i;
-}
-
-__global__ void k_edge_keys(const int32_t* __restrict__ tri, int64_t nt, uint64_t* keys, int32_t* slot) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 3 * nt) return;
-    const int64_t t = i / 3;
-    const int k = (int)(i % 3);
-    const uint32_t a = (uint32_t)tri[3 * t + k], b = (uint32_t)tri[3 * t + (k + 1) % 3];
-    keys[i] = a < b ? ((uint64_t)a << 32 | b) : ((uint64_t)b << 32 | a);
-    slot[i] = (int32_t)i;
-}
-
-__device__ inline int32_t uf_find(int32_t* p, int32_t x) {
-    while (true) {
-        const int32_t px = p[x];
-        if (px == x) return x;
-        const int32_t gx = p[px];
-        if (gx != px) p[x] = gx;  // path halving (benign race: any ancestor is a valid parent)
-        x = gx;
-    }
-}
-
+// the entries of one run are the triangles on one edge: each joins its predecessor's cluster
 __global__ void k_union_edges(const uint64_t* __restrict__ keys, const int32_t* __restrict__ slot, int64_t m,
                               int32_t* parent) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0 || i >= m || keys[i] != keys[i - 1]) return;
-    int32_t a = slot[i - 1] / 3, b = slot[i] / 3;
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a > b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        if (atomicCAS(&parent[b], b, a) == b) return;
-    }
+    if (i >= m || run_head(keys, i, keys[i])) return;
+    uf_union(parent, slot[i - 1] / 3, slot[i] / 3);
 }
 
 // Cluster sizes: lanes of a wave mostly share one root (neighbouring triangles), so the wave adds
@@ -279,10 +246,7 @@ __global__ void k_areas(const float* __restrict__ pos, const int32_t* __restrict
 __global__ void k_nonmanifold_members(const uint64_t* __restrict__ keys, int64_t m, uint8_t* flag) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const uint64_t k = keys[i];
-    const bool p1 = i >= 1 && keys[i - 1] == k, p2 = i >= 2 && keys[i - 2] == k;
-    const bool n1 = i + 1 < m && keys[i + 1] == k, n2 = i + 2 < m && keys[i + 2] == k;
-    flag[i] = (p1 && p2) || (p1 && n1) || (n1 && n2);
+    flag[i] = run_over_two(keys, m, i);
 }
 
 // key, triangle and area of each member entry (for the host's resolution pass)
@@ -313,8 +277,6 @@ __global__ void k_gather_f64(const double* __restrict__ a, const int32_t* __rest
 }
 
 // ------------------------------------------------------------------ host helpers
-inline unsigned nb(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
-
 // Scratch: a bump arena over one grow-only device buffer cached per device (the ~40 buffers of a
 // filter pass cost no hipMalloc / hipFree -- each hipFree synchronises the device, and the
 // stream-ordered pool still spent ~66 us per hipFreeAsync); release() pops the top allocation.
@@ -323,14 +285,13 @@ inline unsigned nb(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 2
 struct Arena {
     GrowBuf buf;
     bool busy = false;
-    hipStream_t s = nullptr;  // cached with the arena: creating a stream costs ~2 ms
 };
 static std::mutex g_arena_mu;
 static Arena g_arena[kMaxDevices];
+static StreamTable g_streams;  // the cached arena's stream; a private arena brings its own
 
 struct Ctx {
     hipStream_t s = nullptr;
-    int device = 0;
     Arena* ar = nullptr;
     Arena priv;
     size_t top = 0;
@@ -338,7 +299,6 @@ struct Ctx {
     std::vector<void*> owned;                        // fallback allocations
 
     int open(int dev, size_t want) {
-        device = dev;
         {
             std::lock_guard<std::mutex> lk(g_arena_mu);
             if (dev >= 0 && dev < kMaxDevices && !g_arena[dev].busy) {
@@ -346,9 +306,13 @@ struct Ctx {
                 ar->busy = true;
             }
         }
-        if (!ar) ar = &priv;
-        if (!ar->s && hipStreamCreateWithFlags(&ar->s, hipStreamNonBlocking) != hipSuccess) return 1;
-        s = ar->s;
+        if (ar) {
+            s = g_streams.get(dev);
+        } else {
+            ar = &priv;
+            if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
+        }
+        if (!s) return 1;
         return ar->buf.reserve(want, want) != hipSuccess;
     }
     template <class T>
@@ -384,13 +348,14 @@ struct Ctx {
         }
     }
     ~Ctx() {
-        if (!s) return;
-        for (void* p : owned) (void)hipFreeAsync(p, s);
-        (void)hipStreamSynchronize(s);
+        if (s) {
+            for (void* p : owned) (void)hipFreeAsync(p, s);
+            (void)hipStreamSynchronize(s);
+        }
         if (ar == &priv) {
             if (priv.buf.p) (void)hipFree(priv.buf.p);
-            (void)hipStreamDestroy(priv.s);
-        } else if (ar) {
+            if (s) (void)hipStreamDestroy(s);
+        } else if (ar) {  // also after a failed open(): the cached arena is not left marked busy
             std::lock_guard<std::mutex> lk(g_arena_mu);
             ar->busy = false;
         }
@@ -404,53 +369,47 @@ struct Ctx {
         return 1;                                                                \
     }
 
+// hipcub's two-phase call, run(temp, temp_bytes) being the hipcub function bound to its arguments: the size
+// query (temp == nullptr), temp storage from the arena, the run (`sync`: then a wait), the stream-ordered release.
+template <class Run>
+static int cub_call(Ctx& c, bool sync, Run run) {
+    size_t tb = 0;
+    MQR_CHECK_HIP(run(nullptr, tb));
+    MF_ALLOC(tmp, char, (int64_t)tb + 16);
+    MQR_CHECK_HIP(run(tmp, tb));
+    if (sync) MQR_CHECK_HIP(hipStreamSynchronize(c.s));
+    c.release(tmp);
+    return 0;
+}
+
 // order-preserving list of indices i in [0, n) with flag[i] != 0
 template <class F>
 static int select_flagged(Ctx& c, const F* flags, int64_t n, int32_t* out, int64_t* count) {
     hipcub::CountingInputIterator<int32_t> it(0);
-    int32_t* d_num = c.alloc<int32_t>(1);
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, it, flags, out, d_num, (int)n, c.s));
-    void* tmp = c.alloc<char>((int64_t)tb + 16);
-    if (!d_num || !tmp) {
-        set_error("mesh filter: device allocation failed");
+    MF_ALLOC(d_num, int32_t, 1);
+    if (cub_call(c, false, [&](void* tmp, size_t& tb) {
+            return hipcub::DeviceSelect::Flagged(tmp, tb, it, flags, out, d_num, (int)n, c.s);
+        }))
         return 1;
-    }
-    MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(tmp, tb, it, flags, out, d_num, (int)n, c.s));
     int32_t h = 0;
     MQR_CHECK_HIP(hipMemcpyAsync(&h, d_num, sizeof(int32_t), hipMemcpyDeviceToHost, c.s));
     MQR_CHECK_HIP(hipStreamSynchronize(c.s));
-    c.release(tmp);
     c.release(d_num);
     *count = h;
     return 0;
 }
 
 static int exclusive_sum(Ctx& c, const int32_t* in, int32_t* out, int64_t n) {
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, (int)n, c.s));
-    void* tmp = c.alloc<char>((int64_t)tb + 16);
-    if (!tmp) {
-        set_error("mesh filter: device allocation failed");
-        return 1;
-    }
-    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, c.s));
-    c.release(tmp);  // stream-ordered reuse: later work on c.s runs after the scan
-    return 0;
+    return cub_call(c, false, [&](void* tmp, size_t& tb) {
+        return hipcub::DeviceScan::ExclusiveSum(tmp, tb, in, out, (int)n, c.s);
+    });
 }
 
 template <class K>
 static int sort_pairs(Ctx& c, const K* kin, K* kout, const int32_t* vin, int32_t* vout, int64_t n, int bits) {
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, kin, kout, vin, vout, (int)n, 0, bits, c.s));
-    void* tmp = c.alloc<char>((int64_t)tb + 16);
-    if (!tmp) {
-        set_error("mesh filter: device allocation failed");
-        return 1;
-    }
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, vin, vout, (int)n, 0, bits, c.s));
-    c.release(tmp);
-    return 0;
+    return cub_call(c, false, [&](void* tmp, size_t& tb) {
+        return hipcub::DeviceRadixSort::SortPairs(tmp, tb, kin, kout, vin, vout, (int)n, 0, bits, c.s);
+    });
 }
 
 // Mesh under edit: device arrays owned by the Ctx (replaced as steps compact them).
@@ -574,18 +533,10 @@ static int remove_duplicated_vertices(Ctx& c, Mesh& m) {
     if (sort_pairs(c, kxy, kxys, idx1, idx2, n, 64)) return 1;
     hipLaunchKernelGGL(k_vtx_heads, dim3(nb(n)), dim3(256), 0, c.s, m.pos, idx2, n, head);
     MQR_CHECK_HIP(hipGetLastError());
-    {
-        size_t tb = 0;
-        MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveScan(nullptr, tb, head, start, MaxOp(), (int)n, c.s));
-        void* tmp = c.alloc<char>((int64_t)tb + 16);
-        if (!tmp) {
-            set_error("mesh filter: device allocation failed");
-            return 1;
-        }
-        MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveScan(tmp, tb, head, start, MaxOp(), (int)n, c.s));
-        MQR_CHECK_HIP(hipStreamSynchronize(c.s));
-        c.release(tmp);
-    }
+    if (cub_call(c, true, [&](void* tmp, size_t& tb) {
+            return hipcub::DeviceScan::InclusiveScan(tmp, tb, head, start, MaxOp(), (int)n, c.s);
+        }))
+        return 1;
     hipLaunchKernelGGL(k_vtx_rep, dim3(nb(n)), dim3(256), 0, c.s, idx2, start, n, rep, keepv);
     MQR_CHECK_HIP(hipGetLastError());
     if (exclusive_sum(c, keepv, newidx, n)) return 1;
@@ -617,7 +568,7 @@ static int remove_non_manifold_edges(Ctx& c, Mesh& m, int64_t* removed) {
         MF_ALLOC(slot_s, int32_t, ne);
         MF_ALLOC(flag, uint8_t, ne);
         MF_ALLOC(mem, int32_t, ne);
-        hipLaunchKernelGGL(k_edge_keys, dim3(nb(ne)), dim3(256), 0, c.s, m.tri, n, keys, slot);
+        hipLaunchKernelGGL(k_edge_keys<false>, dim3(nb(ne)), dim3(256), 0, c.s, m.tri, n, (uint64_t)0, keys, slot);
         MQR_CHECK_HIP(hipGetLastError());
         if (sort_pairs(c, keys, keys_s, slot, slot_s, ne, 64)) return 1;
         hipLaunchKernelGGL(k_nonmanifold_members, dim3(nb(ne)), dim3(256), 0, c.s, keys_s, ne, flag);
@@ -739,7 +690,7 @@ int mqr_mesh_filter_components(int device, const float* vertices, const float* n
         MQR_REQUIRE(parent && keys && keys_s && slot && slot_s && count && is_root && cid,
                     "mesh filter: device allocation failed");
         hipLaunchKernelGGL(k_iota, dim3(nb(nt)), dim3(256), 0, c.s, parent, nt);
-        hipLaunchKernelGGL(k_edge_keys, dim3(nb(ne)), dim3(256), 0, c.s, m.tri, nt, keys, slot);
+        hipLaunchKernelGGL(k_edge_keys<false>, dim3(nb(ne)), dim3(256), 0, c.s, m.tri, nt, (uint64_t)0, keys, slot);
         MQR_CHECK_HIP(hipGetLastError());
         if (sort_pairs(c, keys, keys_s, slot, slot_s, ne, 64)) return 1;
         hipLaunchKernelGGL(k_union_edges, dim3(nb(ne)), dim3(256), 0, c.s, keys_s, slot_s, ne, parent);
@@ -811,13 +762,13 @@ int mqr_mesh_filter_components(int device, const float* vertices, const float* n
     }
     stats[6] = m.nt;
     stats[7] = m.nv;
-    // copy the result out of the scratch arena into one allocation owned by the geometry object
-    mqr_geom* g = new mqr_geom();
+    // copy the result out of the scratch arena into one allocation owned by the geometry object (held by a
+    // guard: every error exit below frees it and returns its block to the cache)
+    std::unique_ptr<mqr_geom, int (*)(mqr_geom*)> g(new mqr_geom(), mqr_geom_free);
     g->device = device;
     g->nv = m.nv;
     g->nt = m.nt;
-    if (geom_alloc(g, m.nv, m.nt)) {
-        delete g;
+    if (geom_alloc(g.get(), m.nv, m.nt)) {
         set_error("mesh filter: device allocation failed");
         return 1;
     }
@@ -828,7 +779,7 @@ int mqr_mesh_filter_components(int device, const float* vertices, const float* n
         MQR_CHECK_HIP(hipMemsetAsync(g->nrm, 0, (char*)g->tri - (char*)g->nrm, c.s));
     if (m.nt) MQR_CHECK_HIP(hipMemcpyAsync(g->tri, m.tri, sizeof(int32_t) * 3 * m.nt, hipMemcpyDeviceToDevice, c.s));
     MQR_CHECK_HIP(hipStreamSynchronize(c.s));
-    *out = g;
+    *out = g.release();
     return 0;
 }
 

@@ -8,26 +8,27 @@
 // Device work: an index check and a vertex pass (finite check, bounding box by integer atomics on
 // order-preserving keys) -> host reads two flags -> density histogram (LDS, integer atomics) ->
 // per-triangle shape terms and unnormalised normals -> stable radix sort of the corner list by vertex id
-// and one walk per vertex (vertex normals in Open3D's accumulation order, no float atomics) -> edge keys
-// (u64, u == v edges get a key past every real one) -> radix sort -> union-find over vertices by run
-// heads -> two passes over run heads (sums, then squared deviations from the means).  Every mean and std
-// is an order-fixed float64 reduction (per-lane partials, wave butterfly, waves in order through LDS,
-// slabs summed by one workgroup in a fixed order, the pattern of pair_reduce.hpp), so a repeated call is
-// bit-identical.  Scratch is one block of the device-block cache.
+// and one walk per vertex (vertex normals in Open3D's accumulation order, no float atomics) -> the sorted
+// edge list of mesh_edges.hpp (loop edges dropped) -> its union-find over vertices by run heads -> two
+// passes over run heads (sums, then squared deviations from the means).  Every mean and std is an
+// order-fixed float64 reduction (pair_reduce.hpp's slab per workgroup, the slabs summed by one workgroup
+// in a fixed order), so a repeated call is bit-identical.  Scratch is one block of the device-block cache.
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
-#include <mutex>
 #include <string>
 
 #include "device_block.hpp"
+#include "mesh_edges.hpp"
 #include "mqr_common.hpp"
+#include "pair_reduce.hpp"
 
 namespace mqr {
 namespace mq {
+using namespace edges;
 
-constexpr int kT = 256;                       // lanes of every workgroup here
+constexpr int kT = pairsum::kThreads;         // lanes of every workgroup here
 constexpr int kPer = 4;                       // items per lane of the reducing kernels
 constexpr int kTile = kT * kPer;              // items per workgroup (and per slab)
 constexpr int kNS = 7;                        // sums of a slab
@@ -64,28 +65,20 @@ __device__ inline float order_val(uint32_t k) {
 }
 
 // ------------------------------------------------------------------ order-fixed reductions
-// The workgroup's kNS sums, minimum and maximum into slab[0..kSlab).  Every lane calls it, once per kernel.
+// The workgroup's kNS sums (pair_reduce.hpp), min and max into slab[0..kSlab).  Every lane calls it, once per kernel.
 __device__ inline void block_to_slab(const double (&acc)[kNS], double mn, double mx, double* __restrict__ slab) {
-    __shared__ double sh[kT / 64][kSlab];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int j = 0; j < kNS; ++j) {
-        double v = acc[j];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        if (lane == 0) sh[wave][j] = v;
-    }
+    __shared__ double sh[pairsum::kWaves][kNS];
+    __shared__ double shm[pairsum::kWaves][2];
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) {
         mn = fmin(mn, __shfl_xor(mn, off, 64));
         mx = fmax(mx, __shfl_xor(mx, off, 64));
     }
-    if (lane == 0) sh[wave][kNS] = mn, sh[wave][kNS + 1] = mx;
-    __syncthreads();
-    const int j = threadIdx.x;
-    if (j < kNS) slab[j] = ((sh[0][j] + sh[1][j]) + sh[2][j]) + sh[3][j];
-    else if (j == kNS) slab[j] = fmin(fmin(sh[0][j], sh[1][j]), fmin(sh[2][j], sh[3][j]));
-    else if (j == kNS + 1) slab[j] = fmax(fmax(sh[0][j], sh[1][j]), fmax(sh[2][j], sh[3][j]));
+    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6][0] = mn, shm[threadIdx.x >> 6][1] = mx;
+    pairsum::block_sums_to_slab(acc, sh, slab);  // its barrier also covers shm
+    const int j = (int)threadIdx.x - kNS;
+    if (j == 0) slab[kNS] = fmin(fmin(shm[0][0], shm[1][0]), fmin(shm[2][0], shm[3][0]));
+    else if (j == 1) slab[kNS + 1] = fmax(fmax(shm[0][1], shm[1][1]), fmax(shm[2][1], shm[3][1]));
 }
 
 // One workgroup: lane l adds slabs l, l + kT, ... in that order, then the workgroup reduces as above.
@@ -320,51 +313,13 @@ __global__ void k_vertex_normals(const uint32_t* __restrict__ key, const int32_t
 }
 
 // ------------------------------------------------------------------ edges
-// Entry 3 t + e is the edge (i_e, i_{e+1}) of triangle t as (min << 32 | max); an edge with u == v gets
-// `none` = (nv << 32 | nv), past every real key, so the dropped entries sort to the end.
-__global__ void k_edge_keys(const int32_t* __restrict__ tri, int64_t nt, uint64_t none, uint64_t* keys, int32_t* slot) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 3 * nt) return;
-    const int64_t t = i / 3;
-    const int k = (int)(i % 3);
-    const uint32_t a = (uint32_t)tri[3 * t + k], b = (uint32_t)tri[3 * t + (k + 1) % 3];
-    keys[i] = a == b ? none : a < b ? ((uint64_t)a << 32 | b) : ((uint64_t)b << 32 | a);
-    slot[i] = (int32_t)i;
-}
-
-__global__ void k_iota(int32_t* a, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = (int32_t)i;
-}
-
-__device__ inline int32_t uf_find(int32_t* p, int32_t x) {
-    while (true) {
-        const int32_t px = p[x];
-        if (px == x) return x;
-        const int32_t gx = p[px];
-        if (gx != px) p[x] = gx;  // path halving (benign race: any ancestor is a valid parent)
-        x = gx;
-    }
-}
-
-// union-find over vertices, hooked by each distinct edge (larger root under smaller)
+// union-find over vertices, hooked by each distinct edge
 __global__ void k_union_vertices(const uint64_t* __restrict__ keys, int64_t m, uint64_t none, int32_t* parent) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
     const uint64_t k = keys[i];
-    if (k == none || (i > 0 && keys[i - 1] == k)) return;
-    int32_t a = (int32_t)(k >> 32), b = (int32_t)(uint32_t)k;
-    while (true) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a > b) {
-            const int32_t t = a;
-            a = b;
-            b = t;
-        }
-        if (atomicCAS(&parent[b], b, a) == b) return;
-    }
+    if (k == none || !run_head(keys, i, k)) return;
+    uf_union(parent, (int32_t)(k >> 32), (int32_t)(uint32_t)k);
 }
 
 // Hooks only ever re-parent a root and halving only writes non-roots, so after the unions the roots are
@@ -397,9 +352,8 @@ __global__ void __launch_bounds__(kT) k_edge_pass(const uint64_t* __restrict__ k
         const int64_t i = (int64_t)blockIdx.x * kTile + kk * kT + threadIdx.x;
         if (i >= m) continue;
         const uint64_t k = keys[i];
-        if (k == none || (i > 0 && keys[i - 1] == k)) continue;
-        int mult = 1;
-        if (i + 1 < m && keys[i + 1] == k) mult = (i + 2 < m && keys[i + 2] == k) ? 3 : 2;
+        if (k == none || !run_head(keys, i, k)) continue;
+        const int mult = run_length3(keys, m, i);
         const int64_t u = (int64_t)(k >> 32), v = (int64_t)(uint32_t)k;
         if (PASS == 0) {
             acc[0] += 1.0;
@@ -436,20 +390,7 @@ __global__ void __launch_bounds__(kT) k_edge_pass(const uint64_t* __restrict__ k
 }
 
 // ------------------------------------------------------------------ host
-inline unsigned nb(int64_t n, int per = kT) { return (unsigned)std::max<int64_t>((n + per - 1) / per, 1); }
-
-static std::mutex g_stream_mu;
-static hipStream_t g_stream[kMaxDevices];  // one per device, created on first use (creating a stream costs ~2 ms)
-
-static hipStream_t quality_stream(int device) {
-    std::lock_guard<std::mutex> lk(g_stream_mu);
-    if (device < 0 || device >= kMaxDevices) return nullptr;
-    if (!g_stream[device] && hipStreamCreateWithFlags(&g_stream[device], hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        g_stream[device] = nullptr;
-    }
-    return g_stream[device];
-}
+static StreamTable g_streams;
 
 static int ceil_log2(int64_t n) {
     int b = 0;
@@ -473,7 +414,7 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
     MQR_REQUIRE(loc == MQR_HOST || loc == MQR_DEVICE, "mesh quality: loc must be MQR_HOST or MQR_DEVICE");
     MQR_REQUIRE(nt < ((int64_t)1 << 31) / 3 && nv < ((int64_t)1 << 31), "mesh quality: mesh too large (3 nt >= 2^31)");
     MQR_CHECK_HIP(hipSetDevice(device));
-    hipStream_t s = quality_stream(device);
+    hipStream_t s = g_streams.get(device);
     MQR_REQUIRE(s, "mesh quality: no stream for the device");
 
     const int64_t m = 3 * nt;
@@ -572,7 +513,7 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
         MQR_CHECK_HIP(hipGetLastError());
     }
     // ---- topology
-    hipLaunchKernelGGL(k_edge_keys, dim3(nb(m)), dim3(kT), 0, s, tri, nt, none, keys, slot);
+    hipLaunchKernelGGL(k_edge_keys<true>, dim3(nb(m)), dim3(kT), 0, s, tri, nt, none, keys, slot);
     MQR_CHECK_HIP(hipGetLastError());
     {
         size_t t2 = tb;

@@ -112,16 +112,18 @@ def project_vertex_colors(mesh, images, K, T_wc, device=0, complete=True, **kw):
     """Ray-cast each keyframe's colour-aligned depth from `mesh` (raycast_in_color_view), then colour
     the vertices: color_map (complete=True) or the visibility-and-average primitive color_vertices.
     Returns (colours, counts)."""
-    from .raycasting import RaycastingScene, _device_mesh, _mesh_arrays
+    from .geometry import device_mesh, host_rows, mesh_fields
+    from .raycasting import RaycastingScene
     im = np.asarray(images)
     N, H, W = im.shape[:3]
     scene = RaycastingScene(device=device)
-    if _device_mesh(mesh, None, device) is not None:  # the mesh stays in HBM from extraction to colours
-        v = mesh.vertex.positions
+    f = mesh_fields(mesh)
+    if device_mesh(f, device) is not None:  # the mesh stays in HBM from extraction to colours
+        v = f.positions
         scene.add_triangles(mesh)
     else:
-        v, t = _mesh_arrays(mesh)
-        scene.add_triangles(v, t)
+        v = host_rows(f.positions, np.float32)
+        scene.add_triangles(v, host_rows(f.triangles, np.int32))
     depth = scene.cast_pinhole(np.asarray(K, np.float64).reshape(N, 3, 3), np.asarray(T_wc, np.float64).reshape(N, 4, 4),
                                W, H)["t_hit"]
     if complete:

@@ -15,11 +15,11 @@ from __future__ import annotations
 import numpy as np
 
 from .color import ColorMapOptimizer, RigidOptimizerOption
-from .geometry import Tensor
+from .geometry import Tensor, device_mesh, mesh_fields
 from .meshfilter import filter_mesh_components
 from .models import CoordinateSystem, Side, Transforms
 from .o3d_utils import dataset_intrinsics_extrinsics, extrinsics_to_transforms
-from .raycasting import RaycastingScene, _device_mesh
+from .raycasting import RaycastingScene
 from .vbg import parse_device
 
 
@@ -53,7 +53,7 @@ def optimize_color_pose(vbg, data_io, config, sides=None):
 
     device = parse_device(getattr(mesh, "device", None) or getattr(config, "device", None))
     scene = RaycastingScene(device=device)
-    on_device = _device_mesh(mesh, None, device) is not None
+    on_device = device_mesh(mesh_fields(mesh), device) is not None
     if on_device:
         scene.add_triangles(mesh)
     else:

@@ -20,6 +20,7 @@ from typing import List, Optional
 import numpy as np
 
 from ._lib import MQR_DEVICE, MQR_HOST, call, ptr
+from .geometry import device_mesh, host_array, mesh_fields
 
 
 @dataclass
@@ -123,69 +124,29 @@ def _run(device, pv, nv, pc, pt, nt, loc, name, path):
     return RawMeshMetrics(name=name, path=path, **kw)
 
 
-def _device_mesh(mesh):
-    """(device, positions ptr, nv, colours ptr or None, triangles ptr, nt) of a tensor mesh held in HBM."""
-    from .geometry import device_ptr
-    from .vbg import parse_device
-    if not (hasattr(mesh, "vertex") and hasattr(mesh, "triangle")):
-        return None
-    v, t = mesh.vertex.positions, mesh.triangle.indices
-    pv = device_ptr(v)
-    if pv is None or v.dtype != np.float32 or t.dtype != np.int32:
-        return None
-    dev = pv[1]
-    pt = device_ptr(t, dev)
-    if pt is None:
-        return None
-    if getattr(mesh, "device", None) is not None and parse_device(mesh.device) != dev:
-        return None
-    c = mesh.vertex.get("colors")
-    pc = None
-    if c is not None:
-        pc = device_ptr(c, dev)
-        if pc is None or c.dtype != np.float32 or tuple(c.shape) != tuple(v.shape):
-            return None  # colours elsewhere: take the host path for the whole mesh
-    return dev, pv[0], v.shape[0], None if pc is None else pc[0], pt[0], t.shape[0]
-
-
-def _as_array(x):
-    return x.numpy() if hasattr(x, "numpy") else np.asarray(x)
-
-
 def compute_raw_metrics(mesh, name: str = "", path=None, device: int = 0) -> RawMeshMetrics:
     """The reference's raw metrics of one mesh, computed on the GPU.
 
-    ``mesh`` is a tensor mesh (one held in HBM is read in place, colours from ``mesh.vertex["colors"]``
-    when present), an object with ``vertices`` / ``triangles`` / optional ``vertex_colors``, or a
-    ``(vertices, triangles[, colors])`` tuple.  Host arrays are checked with numpy (shape, finite values,
-    index range) and raise ``ValueError`` before anything is launched.  Positions and colours are float32
-    on the device: float64 inputs are rounded to float32, then all arithmetic is float64.
+    ``mesh`` is anything ``geometry.mesh_fields`` unpacks; a tensor mesh held in HBM is read in place
+    (``geometry.device_mesh``).  Host arrays are checked with numpy (shape, finite values, index range) and
+    raise ``ValueError`` before anything is launched.  Positions and colours are float32 on the device:
+    float64 inputs are rounded to float32, then all arithmetic is float64.
     """
-    d = _device_mesh(mesh) if not isinstance(mesh, (tuple, list)) else None
+    f = mesh_fields(mesh)
+    d = device_mesh(f, colors=True, strict=True)
     if d is not None:
-        dev, pv, nv, pc, pt, nt = d
-        if nv == 0 or nt == 0:
-            raise ValueError(f"Mesh {path} has no geometry (vertices={nv}, triangles={nt})")
-        return _run(dev, ctypes.c_void_p(pv), nv, None if pc is None else ctypes.c_void_p(pc), ctypes.c_void_p(pt), nt,
-                    MQR_DEVICE, name, path)
-    if isinstance(mesh, (tuple, list)):
-        if len(mesh) not in (2, 3):
-            raise ValueError("expected (vertices, triangles[, colors])")
-        v, t = mesh[0], mesh[1]
-        c = mesh[2] if len(mesh) == 3 else None
-    elif hasattr(mesh, "vertex") and hasattr(mesh, "triangle"):
-        v, t, c = mesh.vertex.positions, mesh.triangle.indices, mesh.vertex.get("colors")
+        if d.nv == 0 or d.nt == 0:
+            raise ValueError(f"Mesh {path} has no geometry (vertices={d.nv}, triangles={d.nt})")
+        pc = None if d.colors is None else ctypes.c_void_p(d.colors)
+        return _run(d.device, ctypes.c_void_p(d.positions), d.nv, pc, ctypes.c_void_p(d.triangles), d.nt, MQR_DEVICE,
+                    name, path)
+    if f.kind == "tensor" and f.device is not None:
         from .vbg import parse_device
-        if getattr(mesh, "device", None) is not None:
-            device = parse_device(mesh.device)
-    else:
-        v, t, c = mesh.vertices, mesh.triangles, getattr(mesh, "vertex_colors", None)
-        if hasattr(mesh, "has_vertex_colors") and not mesh.has_vertex_colors():
-            c = None
-    c = None if c is None else _as_array(c)
+        device = parse_device(f.device)
+    c = None if f.colors is None else host_array(f.colors)
     if c is not None and c.size == 0:
         c = None
-    v, t, c = _host_mesh(_as_array(v), _as_array(t), c)
+    v, t, c = _host_mesh(host_array(f.positions), host_array(f.triangles), c)
     return _run(device, ptr(v), v.shape[0], None if c is None else ptr(c), ptr(t), t.shape[0], MQR_HOST, name, path)
 
 

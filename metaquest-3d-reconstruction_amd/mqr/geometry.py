@@ -18,6 +18,7 @@ device arrays in place, so extract -> filter -> cast -> colour moves no mesh ove
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -136,6 +137,103 @@ def device_ptr(x, device_id=None):
     if d is None or (device_id is not None and d.device_id != int(device_id)):
         return None
     return d.ptr, d.device_id
+
+
+class MeshFields(NamedTuple):
+    """A mesh's raw fields as its holder keeps them (Tensors, arrays or lists; None for what is absent)."""
+    positions: object
+    triangles: object
+    normals: object
+    colors: object
+    kind: str      # "tensor", "legacy", "tuple" or "loose"
+    device: object  # the mesh object's ``device`` attribute, if it has one
+
+
+def mesh_fields(mesh, triangles=None) -> MeshFields:
+    """Unpack a tensor mesh (``.vertex`` / ``.triangle``), a legacy mesh (``.vertices`` / ``.triangles`` /
+    ``.vertex_normals`` / ``.vertex_colors``, no colours when ``has_vertex_colors()`` says so), a
+    ``(vertices, triangles[, colors])`` tuple, or a loose ``vertices, triangles`` pair."""
+    if triangles is not None:
+        return MeshFields(mesh, triangles, None, None, "loose", None)
+    if isinstance(mesh, (tuple, list)):
+        if len(mesh) not in (2, 3):
+            raise ValueError("expected (vertices, triangles[, colors])")
+        return MeshFields(mesh[0], mesh[1], None, mesh[2] if len(mesh) == 3 else None, "tuple", None)
+    dev = getattr(mesh, "device", None)
+    if hasattr(mesh, "vertex") and hasattr(mesh, "triangle"):
+        vx = mesh.vertex
+        return MeshFields(vx.positions, mesh.triangle.indices, getattr(vx, "normals", None),
+                          getattr(vx, "colors", None), "tensor", dev)
+    c = getattr(mesh, "vertex_colors", None)
+    if hasattr(mesh, "has_vertex_colors") and not mesh.has_vertex_colors():
+        c = None
+    return MeshFields(mesh.vertices, mesh.triangles, getattr(mesh, "vertex_normals", None), c, "legacy", dev)
+
+
+class DeviceMesh(NamedTuple):
+    """Device pointers and counts of a mesh held in HBM; normals / colors are None unless requested and fit."""
+    device: int
+    positions: int
+    nv: int
+    triangles: int
+    nt: int
+    normals: Optional[int]
+    colors: Optional[int]
+
+
+def device_mesh(f: MeshFields, device_id=None, normals=False, colors=False, strict=False) -> Optional[DeviceMesh]:
+    """The mesh in place, when positions (float32, trailing dimension 3) and triangles (int32, trailing
+    dimension 3) are both in HBM on one device; None sends the caller down its host path.
+
+    Only tensor meshes and loose pairs qualify: a legacy mesh or a tuple never takes the device path.  The
+    counts are the products of the leading dimensions, so loose ``(H, W, 3)`` Tensors are accepted.  With
+    ``device_id`` both arrays must live on that device.  Without it the device is the positions' own, and a
+    ``mesh.device`` that names another device gives None.  A requested optional field is returned when it is
+    on that device, float32 and shaped like the positions; one that is absent or unfit has the pointer None,
+    and with ``strict`` one that is present but unfit gives None for the whole mesh.  The consumers' rules:
+
+    * filter_mesh_components: ``device_id`` is ``parse_device(mesh.device)``.  Unfit normals are left out:
+      the filter runs without them and the result's normals are zeros.  (On its host path, normals whose row
+      count differs from the positions' are dropped.)  Zero triangles returns the input object with the
+      reference's warning, on either path.
+    * compute_raw_metrics: no ``device_id``, colours ``strict``: unfit colours send the whole mesh down the
+      host path, where an empty colour array counts as no colours and every array is validated with numpy.
+      A device mesh with ``nv == 0`` or ``nt == 0`` raises ValueError.
+    * RaycastingScene.add_triangles and the colour stages: ``device_id`` is the scene's device; positions and
+      triangles only.
+    """
+    if f.kind not in ("tensor", "loose"):
+        return None
+    v, t = f.positions, f.triangles
+    pv = device_ptr(v, device_id)
+    pt = None if pv is None else device_ptr(t, pv[1])
+    if pt is None or v.dtype != np.float32 or t.dtype != np.int32 or v.shape[-1:] != (3,) or t.shape[-1:] != (3,):
+        return None
+    dev = pv[1]
+    if device_id is None and f.device is not None:
+        from .vbg import parse_device
+        if parse_device(f.device) != dev:
+            return None
+
+    def fit(x, wanted):
+        ok = wanted and x is not None and x.dtype == np.float32 and tuple(x.shape) == tuple(v.shape)
+        p = device_ptr(x, dev) if ok else None
+        return None if p is None else p[0]
+
+    pn, pc = fit(f.normals, normals), fit(f.colors, colors)
+    unfit = (normals and f.normals is not None and pn is None) or (colors and f.colors is not None and pc is None)
+    if strict and unfit:
+        return None
+    return DeviceMesh(dev, pv[0], int(np.prod(v.shape[:-1])), pt[0], int(np.prod(t.shape[:-1])), pn, pc)
+
+
+def host_array(x) -> np.ndarray:
+    return x.numpy() if hasattr(x, "numpy") else np.asarray(x)
+
+
+def host_rows(x, dtype) -> np.ndarray:
+    """The one host conversion of a mesh field: contiguous, ``dtype`` (float32 / int32), shape (-1, 3)."""
+    return np.ascontiguousarray(host_array(x), dtype=dtype).reshape(-1, 3)
 
 
 def _tensor(x):

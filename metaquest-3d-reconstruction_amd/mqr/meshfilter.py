@@ -15,45 +15,17 @@ import numpy as np
 
 from . import _lib
 from ._lib import MQR_HOST, call, ptr
-from .geometry import Tensor, TriangleMesh
+from .geometry import DeviceGeom, Tensor, TriangleMesh, device_mesh, host_rows, mesh_fields
 
 
-def _device_inputs(mesh, device):
-    """(pos, nrm or None, nv, tri, nt) device pointers when the tensor mesh lives in HBM on `device`."""
-    from .geometry import device_ptr
-    if not (hasattr(mesh, "vertex") and hasattr(mesh, "triangle")):
-        return None
-    v, t = mesh.vertex.positions, mesh.triangle.indices
-    n = mesh.vertex.get("normals")
-    pv, pt = device_ptr(v, device), device_ptr(t, device)
-    if pv is None or pt is None or v.dtype != np.float32 or t.dtype != np.int32:
-        return None
-    pn = device_ptr(n, device) if n is not None and n.shape == v.shape and n.dtype == np.float32 else None
-    return pv[0], None if pn is None else pn[0], v.shape[0], pt[0], t.shape[0]
-
-
-def _arrays(mesh):
-    if hasattr(mesh, "vertex") and hasattr(mesh, "triangle"):
-        v = mesh.vertex.positions
-        n = getattr(mesh.vertex, "normals", None)
-        t = mesh.triangle.indices
-    else:
-        v, t = mesh.vertices, mesh.triangles
-        n = getattr(mesh, "vertex_normals", None)
-    v = np.ascontiguousarray(v.numpy() if hasattr(v, "numpy") else v, dtype=np.float32).reshape(-1, 3)
-    t = np.ascontiguousarray(t.numpy() if hasattr(t, "numpy") else t, dtype=np.int32).reshape(-1, 3)
-    if n is not None:
-        n = np.ascontiguousarray(n.numpy() if hasattr(n, "numpy") else n, dtype=np.float32).reshape(-1, 3)
-        if n.shape[0] != v.shape[0]:
-            n = None
-    return v, n, t
+STAT_KEYS = ("input_triangles", "clusters", "kept_clusters", "small_cluster_triangles", "largest_cluster",
+             "non_manifold_removed", "triangles", "vertices")
 
 
 def filter_mesh_components_gpu(vertices, normals, triangles, min_triangle_count: int = 2000, device: int = 0):
     """Arrays in, (vertices, normals, triangles, stats dict) out."""
-    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
-    t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
-    n = None if normals is None else np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    v, t = host_rows(vertices, np.float32), host_rows(triangles, np.int32)
+    n = None if normals is None else host_rows(normals, np.float32)
     g = ctypes.c_void_p()
     stats = np.zeros(8, np.int64)
     call("mqr_mesh_filter_components", int(device), ptr(v), None if n is None else ptr(n), v.shape[0], ptr(t),
@@ -67,49 +39,46 @@ def filter_mesh_components_gpu(vertices, normals, triangles, min_triangle_count:
         call("mqr_geom_copy", g, ptr(pos), ptr(nrm), ptr(tri) if nt.value else None, MQR_HOST)
     finally:
         call("mqr_geom_free", g)
-    keys = ("input_triangles", "clusters", "kept_clusters", "small_cluster_triangles", "largest_cluster",
-            "non_manifold_removed", "triangles", "vertices")
-    return pos, (nrm if n is not None else None), tri, dict(zip(keys, (int(x) for x in stats)))
+    return pos, (nrm if n is not None else None), tri, dict(zip(STAT_KEYS, (int(x) for x in stats)))
 
 
-def _filter_device(mesh, dev_id, ins, min_triangle_count):
-    """The tensor mesh in HBM, filtered in place of a host round trip; the result stays in HBM."""
-    from .geometry import DeviceGeom
-    pv, pn, nv, pt, nt = ins
+def _filter_device(d, min_triangle_count):
+    """The tensor mesh in HBM (``d``: its DeviceMesh), filtered without a host round trip; the result stays in HBM."""
     g = ctypes.c_void_p()
     stats = np.zeros(8, np.int64)
-    call("mqr_mesh_filter_components", int(dev_id), ctypes.c_void_p(pv), None if pn is None else ctypes.c_void_p(pn), nv,
-         ctypes.c_void_p(pt), nt, _lib.MQR_DEVICE, int(min_triangle_count), ctypes.byref(g), ptr(stats, _lib._i64p))
-    geom = DeviceGeom(g, dev_id)
-    keys = ("input_triangles", "clusters", "kept_clusters", "small_cluster_triangles", "largest_cluster",
-            "non_manifold_removed", "triangles", "vertices")
+    call("mqr_mesh_filter_components", d.device, ctypes.c_void_p(d.positions),
+         None if d.normals is None else ctypes.c_void_p(d.normals), d.nv, ctypes.c_void_p(d.triangles), d.nt,
+         _lib.MQR_DEVICE, int(min_triangle_count), ctypes.byref(g), ptr(stats, _lib._i64p))
+    geom = DeviceGeom(g, d.device)
     p, n, t = geom.tensors()
-    if pn is None:
+    if d.normals is None:
         n = Tensor(np.zeros((geom.nv, 3), np.float32))
-    return p, n, t, dict(zip(keys, (int(x) for x in stats)))
+    return p, n, t, dict(zip(STAT_KEYS, (int(x) for x in stats)))
 
 
 def filter_mesh_components(mesh, min_triangle_count: int = 2000):
     """Drop-in for the reference's filter_mesh_components (o3d_utils.py:241-321).  A mesh in HBM (this
     package's extraction) is filtered there and the result stays there, as the reference's tensor mesh
-    does on its CUDA device."""
+    does on its CUDA device.  Which meshes take the device path: geometry.device_mesh."""
     from .vbg import parse_device
-    dev = getattr(mesh, "device", None)
-    dev_id = parse_device(dev)
-    ins = _device_inputs(mesh, dev_id)
-    if ins is not None:
-        if ins[4] == 0:
-            print("[Warning] Mesh filtering: Input mesh has no triangles, returning as-is")
-            return mesh
-        pos, nrm, tri, st = _filter_device(mesh, dev_id, ins, min_triangle_count)
-        return _report_filter(TriangleMesh(pos, nrm, tri, device=dev), st, min_triangle_count)
-    v, n, t = _arrays(mesh)
-    if t.shape[0] == 0:
+    f = mesh_fields(mesh)
+    dev_id = parse_device(f.device)
+    d = device_mesh(f, dev_id, normals=True)
+    if d is None:
+        v, t = host_rows(f.positions, np.float32), host_rows(f.triangles, np.int32)
+    if (t.shape[0] if d is None else d.nt) == 0:
         print("[Warning] Mesh filtering: Input mesh has no triangles, returning as-is")
         return mesh
-    pos, nrm, tri, st = filter_mesh_components_gpu(v, n, t, min_triangle_count, dev_id)
-    return _report_filter(TriangleMesh(pos, nrm if nrm is not None else np.zeros_like(pos), tri, device=dev), st,
-                          min_triangle_count)
+    if d is not None:
+        pos, nrm, tri, st = _filter_device(d, min_triangle_count)
+    else:
+        n = None if f.normals is None else host_rows(f.normals, np.float32)
+        if n is not None and n.shape[0] != v.shape[0]:
+            n = None
+        pos, nrm, tri, st = filter_mesh_components_gpu(v, n, t, min_triangle_count, dev_id)
+        if nrm is None:
+            nrm = np.zeros_like(pos)
+    return _report_filter(TriangleMesh(pos, nrm, tri, device=f.device), st, min_triangle_count)
 
 
 def _report_filter(out, st, min_triangle_count):

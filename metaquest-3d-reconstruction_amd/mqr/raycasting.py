@@ -18,44 +18,14 @@ host on the first ``.numpy()``), so ``color_map`` can take them without a round 
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
 
 import numpy as np
 
 from . import _lib
 from ._lib import MQR_HOST, call, ptr
-from .geometry import DeviceArray, Tensor, device_ptr
+from .geometry import DeviceArray, Tensor, device_mesh, host_rows, mesh_fields
 
 INVALID_ID = 0xFFFFFFFF
-
-
-def _mesh_arrays(mesh_or_vertices, triangles=None):
-    if triangles is not None:
-        v, t = mesh_or_vertices, triangles
-    elif hasattr(mesh_or_vertices, "vertex") and hasattr(mesh_or_vertices, "triangle"):   # tensor mesh
-        v, t = mesh_or_vertices.vertex.positions, mesh_or_vertices.triangle.indices
-    else:                                                                                # legacy mesh
-        v, t = mesh_or_vertices.vertices, mesh_or_vertices.triangles
-    v = v.numpy() if hasattr(v, "numpy") else np.asarray(v)
-    t = t.numpy() if hasattr(t, "numpy") else np.asarray(t)
-    return (np.ascontiguousarray(v, dtype=np.float32).reshape(-1, 3),
-            np.ascontiguousarray(t, dtype=np.int32).reshape(-1, 3))
-
-
-def _device_mesh(mesh_or_vertices, triangles, device_id):
-    """((vertex ptr, nv), (triangle ptr, nt)) when positions (float32 (n,3)) and indices (int32 (m,3)) are
-    Tensors in HBM on `device_id`, else None."""
-    if triangles is not None:
-        v, t = mesh_or_vertices, triangles
-    elif hasattr(mesh_or_vertices, "vertex") and hasattr(mesh_or_vertices, "triangle"):
-        v, t = mesh_or_vertices.vertex.positions, mesh_or_vertices.triangle.indices
-    else:
-        return None
-    pv, pt = device_ptr(v, device_id), device_ptr(t, device_id)
-    if pv is None or pt is None or v.dtype != np.float32 or t.dtype != np.int32 or v.shape[-1:] != (3,) \
-            or t.shape[-1:] != (3,):
-        return None
-    return (pv[0], int(np.prod(v.shape[:-1]))), (pt[0], int(np.prod(t.shape[:-1])))
 
 
 def _pinhole_params(K, T):
@@ -96,16 +66,15 @@ class RaycastingScene:
 
     def add_triangles(self, vertex_positions, triangle_indices=None) -> int:
         gid = ctypes.c_uint32()
-        dev = _device_mesh(vertex_positions, triangle_indices, self.device_id)
-        if dev is not None:  # the mesh is in HBM on this scene's device: no host round trip
-            (pv, nv), (pt, nt) = dev
-            call("mqr_scene_add_triangles", self._h, ctypes.c_void_p(pv), nv, ctypes.c_void_p(pt), nt, _lib.MQR_DEVICE,
+        f = mesh_fields(vertex_positions, triangle_indices)
+        d = device_mesh(f, self.device_id)
+        if d is not None:  # the mesh is in HBM on this scene's device: no host round trip
+            call("mqr_scene_add_triangles", self._h, ctypes.c_void_p(d.positions), d.nv, ctypes.c_void_p(d.triangles),
+                 d.nt, _lib.MQR_DEVICE, ctypes.byref(gid))
+        else:
+            v, t = host_rows(f.positions, np.float32), host_rows(f.triangles, np.int32)
+            call("mqr_scene_add_triangles", self._h, ptr(v), v.shape[0], ptr(t), t.shape[0], MQR_HOST,
                  ctypes.byref(gid))
-            self._ngeom += 1
-            return int(gid.value)
-        v, t = _mesh_arrays(vertex_positions, triangle_indices)
-        call("mqr_scene_add_triangles", self._h, ptr(v), v.shape[0], ptr(t), t.shape[0], MQR_HOST,
-             ctypes.byref(gid))
         self._ngeom += 1
         return int(gid.value)
 

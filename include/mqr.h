@@ -446,6 +446,75 @@ typedef struct mqr_quality_metrics {
 int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float* colors, const int32_t* triangles,
                      int64_t nt, int loc, mqr_quality_metrics* out);
 
+/* ---- ground-truth comparison (analysis/computation/compare_mesh_to_ground_truth.py) -----------------
+ * The three device primitives behind mqr.compare_mesh_to_ground_truth (rules in DESIGN §2.6).
+ *
+ * Nearest neighbour (Open3D compute_point_cloud_distance, KDTreeFlann.search_knn_vector_3d with k = 1).
+ * create: a search tree over n float32 xyz targets in `loc` memory.  The tree keeps its own Morton-ordered
+ * copy: the caller's buffer (MQR_DEVICE buffers are read in place) is free again on return.  Errors:
+ * n == 0, n >= 2^31, a coordinate that is not finite or beyond 1e18 in magnitude (found by a kernel that
+ * reads but never gathers; within that range the float32 bounds the search prunes on cannot overflow,
+ * which the exactness below depends on).
+ * query: for each of nq float32 xyz queries in `loc` memory the nearest target: dist[i] float64 and
+ * idx[i] int32 (idx may be NULL), in `out_loc` memory.  Rule: d2 = (dx*dx + dy*dy) + dz*dz in float64 on
+ * the widened float32 coordinates, without contraction; dist = sqrt(d2); among targets of equal d2 the
+ * lowest index wins.  The result is exact (a brute-force search gives the same bits) and independent of
+ * the order of the queries.  nq == 0 is a no-op; nq >= 2^31 or a query coordinate that is not finite or
+ * beyond 1e18 in magnitude is an error. */
+typedef struct mqr_nn mqr_nn;
+int mqr_nn_create(int device, const float* targets, int64_t n, int loc, mqr_nn** out);
+int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* dist, int32_t* idx, int out_loc);
+int mqr_nn_destroy(mqr_nn* h);
+
+/* np.mean, np.std (population, two passes), np.min, np.max, np.median and (dist < threshold).sum() of n
+ * non-negative finite float64 values in `loc` memory; only the struct crosses to the host.  Sums run in a
+ * fixed order, so a repeated call is bit-identical; the median comes from a radix sort of the bit patterns
+ * (an even count gives the mean of the two middle values).  Errors: n == 0, n >= 2^31. */
+typedef struct mqr_distance_stats_result {
+    double mean;
+    double std;
+    double min;
+    double max;
+    double median;
+    int64_t count_below; /* values < threshold, strict */
+    int64_t count;       /* n */
+} mqr_distance_stats_result;
+int mqr_distance_stats(int device, const double* dist, int64_t n, int loc, double threshold,
+                       mqr_distance_stats_result* out);
+
+/* One mesh's measures on one edge sort: vertices nv*3 float32, triangles nt*3 int32 in `loc` memory
+ * (MQR_DEVICE buffers are read in place), all arithmetic float64 on the float32 inputs in a fixed order.
+ *   surface_area   sum of 0.5 |(p1 - p0) x (p2 - p0)| (get_surface_area);
+ *   min / max      the axis-aligned bounds, exact;
+ *   volume         |sum of p0 . (p1 x p2) / 6| when is_closed_oriented, else 0.0 (the reference catches
+ *                  Open3D's "not watertight" exception and uses 0.0);
+ *   is_closed_oriented  every edge (loop edges of degenerate triangles included) lies on exactly two
+ *                  triangles that traverse it in opposite directions.  DEVIATION: Open3D's get_volume also
+ *                  refuses vertex-non-manifold and self-intersecting meshes; this pass does not test for
+ *                  either, and reports their signed sum;
+ *   boundary_edges the edges that lie on exactly one triangle.
+ * `boundary` (may be NULL) receives those edges as (min, max) vertex pairs, ascending by their slot
+ * 3 t + e (edge e of triangle t: the order in which the reference's dictionary first meets them), kept in
+ * HBM: mqr_edge_list_count / _copy (2 n int32 into `loc` memory) / _free.  It stays NULL when there are
+ * none.  nt == 0 is allowed: area 0, volume 0, no boundary.  Errors: nv == 0, 3 nt >= 2^31, a non-finite
+ * coordinate, a triangle index outside [0, nv) (found before any gather). */
+typedef struct mqr_mesh_measure_result {
+    double surface_area;
+    double volume;
+    double min_bound[3];
+    double max_bound[3];
+    int64_t is_closed_oriented;
+    int64_t boundary_edges;
+    int64_t num_vertices;
+    int64_t num_triangles;
+} mqr_mesh_measure_result;
+typedef struct mqr_edge_list mqr_edge_list;
+int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_t* triangles, int64_t nt, int loc,
+                     mqr_mesh_measure_result* out, mqr_edge_list** boundary);
+int mqr_edge_list_count(mqr_edge_list* list, int64_t* n);
+int mqr_edge_list_copy(mqr_edge_list* list, int32_t* pairs, int loc);
+int mqr_edge_list_free(mqr_edge_list* list);
+
 /* Fragment registration (refine_fragment_poses.py:122-271): a CLOUD SET of N float32 xyz clouds in
  * HBM and three batched operations over pairs of them, standing in for Open3D's
  * evaluate_registration, multi_scale_icp (point to point) and get_information_matrix.

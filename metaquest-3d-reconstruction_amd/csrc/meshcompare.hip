@@ -1,0 +1,709 @@
+// meshcompare.hip -- the device side of the ground-truth comparison (mqr/compare_mesh_to_ground_truth.py).
+//
+// Reference: analysis/computation/compare_mesh_to_ground_truth.py.  Its Open3D calls come down to three
+// primitives, each an entry point here (rules in DESIGN §2.6):
+//   mqr_nn_*            compute_point_cloud_distance / KDTreeFlann knn 1: the exact nearest target of every
+//                       query over bucket_tree.hpp's Morton-bucket tree, float64 on the widened float32
+//                       coordinates, d2 = (dx dx + dy dy) + dz dz, ties to the lowest target index;
+//   mqr_distance_stats  np.mean / np.std / np.min / np.max / np.median / (x < t).sum() of a distance array:
+//                       order-fixed float64 slab sums (pair_reduce.hpp), the median from a radix sort of the
+//                       bit patterns;
+//   mqr_mesh_measure    get_surface_area, get_axis_aligned_bounding_box, get_volume and the boundary edges of
+//                       count_holes, on one edge sort (mesh_edges.hpp, loop edges kept).
+// The file is built with -ffp-contract=off.  Scratch is one block of the device-block cache per call; a tree
+// and a boundary list own a plain device allocation until they are destroyed.
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "bucket_tree.hpp"
+#include "device_block.hpp"
+#include "mesh_edges.hpp"
+#include "mqr_common.hpp"
+#include "pair_reduce.hpp"
+
+struct mqr_nn {
+    int device = 0;
+    int64_t n = 0;      // targets
+    int64_t P = 1;      // leaves of the complete tree (a power of two >= buckets)
+    int depth = 0;      // levels below the root
+    void* mem = nullptr;
+    float4* lo = nullptr;  // [2 P] node boxes, heap order
+    float4* hi = nullptr;
+    float4* pts = nullptr;  // [n] targets in Morton order: x, y, z, original index bits
+    uint32_t* bb = nullptr;  // the targets' bounds as ordered keys (the frame of the Morton keys)
+};
+
+struct mqr_edge_list {
+    int device = 0;
+    int64_t n = 0;
+    int32_t* pairs = nullptr;  // [n][2] (min, max)
+};
+
+namespace mqr {
+namespace mc {
+using namespace edges;
+
+constexpr int kT = pairsum::kThreads;
+constexpr int kPer = 4;
+constexpr int kTile = kT * kPer;
+constexpr int kNS = 2;          // sums of a slab
+constexpr int kSlab = kNS + 2;  // ... then one min and one max
+
+static StreamTable g_streams;
+
+// ------------------------------------------------------------------ checks
+// Reads the coordinates only; nothing gathers through them before the host has seen the flag.  A coordinate
+// passes when |a| <= limit (a NaN fails the comparison): FLT_MAX asks for finite values, and the search asks for
+// kCoordLimit, inside which the float32 bounds of bucket_tree.hpp cannot overflow: a difference is at most
+// 2e18, three squares of it 1.2e37 < FLT_MAX.  (An overflowed bound is +inf, which would prune a nearer point.)
+constexpr float kCoordLimit = 1e18f;
+__global__ void k_check_finite(const float* __restrict__ a, int64_t n, float limit, int32_t* flag) {
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        bad |= !(fabsf(a[i]) <= limit);
+    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) *flag = 1;
+}
+
+__global__ void k_check_indices(const int32_t* __restrict__ tri, int64_t n, int64_t nv, int32_t* flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && (tri[i] < 0 || (int64_t)tri[i] >= nv)) *flag = 1;
+}
+
+// ------------------------------------------------------------------ nearest neighbour
+// One query per lane, K = 1: the best (d2, index) pair in registers, the traversal stack in LDS (stack-major:
+// lane t's entry e at stk[256 e + t], conflict-free), sized by the host to the tree's depth + 2 (a nearest-
+// first DFS holds one pending sibling per level plus the current pair).  Boxes are pruned and ordered on
+// box_d2_lb, candidates prefiltered on the same float32 bound and compared exactly in float64; (d2, index) is
+// a total order, so neither the visiting order nor the order of the queries changes a result.  Lane t takes
+// query order[t]: the host sorts the queries by their Morton key in the tree's frame, so a wave's 64 queries
+// are neighbours and walk nearly the same nodes, and results scatter back to the caller's order.
+__global__ __launch_bounds__(256) void k_nn1(const float* __restrict__ Q, const int32_t* __restrict__ order, int64_t nq,
+                                             const float4* __restrict__ pts, int64_t n, int64_t P,
+                                             const float4* __restrict__ lo, const float4* __restrict__ hi,
+                                             double* __restrict__ dist, int32_t* __restrict__ idx) {
+    extern __shared__ int32_t stk_lds[];
+    int32_t* stk = stk_lds + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nq) return;
+    const int64_t qi = order[t];
+    const float qf[3] = {Q[3 * qi], Q[3 * qi + 1], Q[3 * qi + 2]};
+    const double q[3] = {qf[0], qf[1], qf[2]};
+    double bd = __builtin_inf();
+    int32_t bi = 0x7fffffff;
+    int sp = 0;
+    stk[256 * sp++] = 1;
+    while (sp) {
+        const int32_t node = stk[256 * --sp];
+        if ((double)box_d2_lb(qf, lo[node], hi[node]) > bd) continue;
+        if (node >= P) {  // bucket
+            const int64_t b = node - P;
+            const int64_t e = min(n, (b + 1) * kBucket);
+            for (int64_t j = b * kBucket; j < e; ++j) {
+                const float4 pt = pts[j];
+                const float fx = qf[0] - pt.x, fy = qf[1] - pt.y, fz = qf[2] - pt.z;
+                if ((double)((fx * fx + fy * fy + fz * fz) * (1.0f - 0x1p-18f)) > bd) continue;
+                const int32_t v = __float_as_int(pt.w);
+                const double dx = q[0] - (double)pt.x, dy = q[1] - (double)pt.y, dz = q[2] - (double)pt.z;
+                const double d2 = (dx * dx + dy * dy) + dz * dz;
+                if (d2 < bd || (d2 == bd && v < bi)) bd = d2, bi = v;
+            }
+        } else {  // nearer child popped first
+            const int32_t a = 2 * node, c = a + 1;
+            const float da = box_d2_lb(qf, lo[a], hi[a]), dc = box_d2_lb(qf, lo[c], hi[c]);
+            stk[256 * sp++] = da <= dc ? c : a;
+            stk[256 * sp++] = da <= dc ? a : c;
+        }
+    }
+    dist[qi] = sqrt(bd);
+    if (idx) idx[qi] = bi;
+}
+
+// ------------------------------------------------------------------ order-fixed reductions
+// The workgroup's kNS sums (pair_reduce.hpp), min and max into slab[0..kSlab).  Every lane calls it, once per kernel.
+__device__ inline void block_to_slab(const double (&acc)[kNS], double mn, double mx, double* __restrict__ slab) {
+    __shared__ double sh[pairsum::kWaves][kNS];
+    __shared__ double shm[pairsum::kWaves][2];
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        mn = fmin(mn, __shfl_xor(mn, off, 64));
+        mx = fmax(mx, __shfl_xor(mx, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6][0] = mn, shm[threadIdx.x >> 6][1] = mx;
+    pairsum::block_sums_to_slab(acc, sh, slab);  // its barrier also covers shm
+    const int j = (int)threadIdx.x - kNS;
+    if (j == 0) slab[kNS] = fmin(fmin(shm[0][0], shm[1][0]), fmin(shm[2][0], shm[3][0]));
+    else if (j == 1) slab[kNS + 1] = fmax(fmax(shm[0][1], shm[1][1]), fmax(shm[2][1], shm[3][1]));
+}
+
+// One workgroup: lane l adds slabs l, l + kT, ... in that order, then the workgroup reduces as above.
+__global__ void __launch_bounds__(kT) k_reduce_slabs(const double* __restrict__ slabs, int64_t nblk,
+                                                     double* __restrict__ out) {
+    double acc[kNS] = {0.0, 0.0};
+    double mn = INFINITY, mx = -INFINITY;
+    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
+        const double* s = slabs + b * kSlab;
+#pragma unroll
+        for (int j = 0; j < kNS; ++j) acc[j] += s[j];
+        mn = fmin(mn, s[kNS]);
+        mx = fmax(mx, s[kNS + 1]);
+    }
+    block_to_slab(acc, mn, mx, out);
+}
+
+// ------------------------------------------------------------------ distance statistics
+struct StatsRes {
+    double r0[kSlab];  // sum, count below the threshold, min, max
+    double r1[kSlab];  // sum of squared deviations from the mean
+    double median;
+};
+
+// PASS 0: [sum x, count of x < thr], min, max.  PASS 1: [sum (x - mean)^2] with the mean from PASS 0.
+template <int PASS>
+__global__ void __launch_bounds__(kT) k_stats(const double* __restrict__ x, int64_t n, double thr,
+                                              const double* __restrict__ r0, double* __restrict__ slabs) {
+    double acc[kNS] = {0.0, 0.0};
+    double mn = INFINITY, mx = -INFINITY;
+    const double mean = PASS == 1 ? r0[0] / (double)n : 0.0;
+    for (int k = 0; k < kPer; ++k) {
+        const int64_t i = (int64_t)blockIdx.x * kTile + k * kT + threadIdx.x;
+        if (i >= n) continue;
+        const double v = x[i];
+        if (PASS == 0) {
+            acc[0] += v;
+            if (v < thr) acc[1] += 1.0;
+            mn = fmin(mn, v);
+            mx = fmax(mx, v);
+        } else {
+            acc[0] += (v - mean) * (v - mean);
+        }
+    }
+    block_to_slab(acc, mn, mx, slabs + (int64_t)blockIdx.x * kSlab);
+}
+
+// numpy's median of the ascending array: the middle value, or the mean of the two middle ones
+__global__ void k_median(const uint64_t* __restrict__ sorted, int64_t n, StatsRes* res) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const double a = __longlong_as_double((long long)sorted[(n - 1) / 2]);
+    const double b = __longlong_as_double((long long)sorted[n / 2]);
+    res->median = (n & 1) ? a : (a + b) / 2.0;
+}
+
+// ------------------------------------------------------------------ mesh measure
+struct MeasureCtrl {
+    uint32_t bb[8];     // bounds as ordered keys: min x y z, max x y z
+    int32_t bad_index;
+    int32_t bad_coord;
+    int32_t open;       // an edge run that is not two opposite traversals
+    int32_t pad;
+    int64_t nboundary;  // DeviceSelect's count
+    double sums[kSlab];  // area, signed volume
+};
+
+// Per triangle: 0.5 |(p1 - p0) x (p2 - p0)| and p0 . (p1 x p2) / 6, one slab per workgroup.
+__global__ void __launch_bounds__(kT) k_tri_measure(const float* __restrict__ pos, const int32_t* __restrict__ tri,
+                                                    int64_t nt, double* __restrict__ slabs) {
+    double acc[kNS] = {0.0, 0.0};
+    for (int k = 0; k < kPer; ++k) {
+        const int64_t t = (int64_t)blockIdx.x * kTile + k * kT + threadIdx.x;
+        if (t >= nt) continue;
+        const int32_t i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+        double p0[3], p1[3], p2[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            p0[a] = (double)pos[3 * (int64_t)i0 + a];
+            p1[a] = (double)pos[3 * (int64_t)i1 + a];
+            p2[a] = (double)pos[3 * (int64_t)i2 + a];
+        }
+        const double ea[3] = {p1[0] - p0[0], p1[1] - p0[1], p1[2] - p0[2]};
+        const double eb[3] = {p2[0] - p0[0], p2[1] - p0[1], p2[2] - p0[2]};
+        const double n0 = ea[1] * eb[2] - ea[2] * eb[1], n1 = ea[2] * eb[0] - ea[0] * eb[2],
+                     n2 = ea[0] * eb[1] - ea[1] * eb[0];
+        acc[0] += 0.5 * sqrt((n0 * n0 + n1 * n1) + n2 * n2);
+        const double c0 = p1[1] * p2[2] - p1[2] * p2[1], c1 = p1[2] * p2[0] - p1[0] * p2[2],
+                     c2 = p1[0] * p2[1] - p1[1] * p2[0];
+        acc[1] += ((p0[0] * c0 + p0[1] * c1) + p0[2] * c2) / 6.0;
+    }
+    block_to_slab(acc, INFINITY, -INFINITY, slabs + (int64_t)blockIdx.x * kSlab);
+}
+
+// slot 3 t + e runs from corner e to corner e + 1 of triangle t: does it go from the lower index to the higher?
+__device__ inline bool ascending(const int32_t* __restrict__ tri, int32_t s) {
+    const int32_t t = s / 3, e = s % 3;
+    return tri[3 * (int64_t)t + e] < tri[3 * (int64_t)t + (e + 1) % 3];
+}
+
+// Run heads of the sorted edge entries: a run of one marks its slot as boundary; any run that is not exactly
+// two traversals in opposite directions clears the closed-and-oriented property.
+__global__ void k_edge_runs(const uint64_t* __restrict__ keys, const int32_t* __restrict__ slot, int64_t m,
+                            const int32_t* __restrict__ tri, uint8_t* __restrict__ bflag, MeasureCtrl* c) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= m) return;
+    const uint64_t k = keys[i];
+    if (!run_head(keys, i, k)) return;
+    const int mult = run_length3(keys, m, i);
+    if (mult == 1) bflag[slot[i]] = 1;
+    if (mult != 2 || ascending(tri, slot[i]) == ascending(tri, slot[i + 1])) c->open = 1;
+}
+
+__global__ void k_boundary_pairs(const int32_t* __restrict__ slots, int64_t nb, const int32_t* __restrict__ tri,
+                                 int32_t* __restrict__ pairs) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nb) return;
+    const int32_t s = slots[i], t = s / 3, e = s % 3;
+    const int32_t a = tri[3 * (int64_t)t + e], b = tri[3 * (int64_t)t + (e + 1) % 3];
+    pairs[2 * i] = min(a, b);
+    pairs[2 * i + 1] = max(a, b);
+}
+
+static int ceil_log2(int64_t n) {
+    int b = 0;
+    while (((int64_t)1 << b) < n) ++b;
+    return b;
+}
+
+static float host_from_ordered(uint32_t u) {
+    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    float f;
+    std::memcpy(&f, &b, sizeof f);
+    return f;
+}
+
+// every exit of a call drains its stream before the scratch block goes back to the cache
+struct Drain {
+    hipStream_t s;
+    ~Drain() { (void)hipStreamSynchronize(s); }
+};
+
+static int alloc_failed(const char* who, size_t want) {
+    (void)hipGetLastError();
+    set_error(std::string(who) + ": device allocation failed (needed " + std::to_string(want) + " bytes)");
+    return 1;
+}
+
+}  // namespace mc
+}  // namespace mqr
+
+using namespace mqr;
+using namespace mqr::mc;
+
+extern "C" {
+
+int mqr_nn_create(int device, const float* targets, int64_t n, int loc, mqr_nn** out) {
+    MQR_REQUIRE(out, "null argument");
+    *out = nullptr;
+    MQR_REQUIRE(n > 0, "nn: the target set is empty");
+    MQR_REQUIRE(targets, "null argument");
+    MQR_REQUIRE(loc == MQR_HOST || loc == MQR_DEVICE, "nn: loc must be MQR_HOST or MQR_DEVICE");
+    MQR_REQUIRE(n < ((int64_t)1 << 31), "nn: too many targets (n >= 2^31)");
+    MQR_CHECK_HIP(hipSetDevice(device));
+    hipStream_t s = g_streams.get(device);
+    MQR_REQUIRE(s, "nn: no stream for the device");
+
+    const int64_t nbk = (n + kBucket - 1) / kBucket;
+    int64_t P = 1;
+    while (P < nbk) P <<= 1;
+    size_t tb = 0;
+    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                     (const int32_t*)nullptr, (int32_t*)nullptr, (int)n, 0, 63, s));
+    const bool host_in = loc == MQR_HOST;
+    const size_t b_pos = host_in ? sizeof(float) * 3 * n : 0;
+    const size_t want = al256(b_pos) + 256 + 2 * al256(sizeof(uint64_t) * n) + 2 * al256(sizeof(int32_t) * n) +
+                        al256(tb + 16) + 256;
+    CachedBlock blk(device, want);
+    if (!blk.p) return alloc_failed("nn", want);
+    float* d_pos = host_in ? (float*)blk.take(b_pos) : nullptr;
+    int32_t* flag = (int32_t*)blk.take(sizeof(int32_t));
+    uint64_t* keys = (uint64_t*)blk.take(sizeof(uint64_t) * n);
+    uint64_t* keys_s = (uint64_t*)blk.take(sizeof(uint64_t) * n);
+    int32_t* ids = (int32_t*)blk.take(sizeof(int32_t) * n);
+    int32_t* sorted = (int32_t*)blk.take(sizeof(int32_t) * n);
+    void* tmp = blk.take(tb + 16);
+    if (!flag || !keys || !keys_s || !ids || !sorted || !tmp || (host_in && !d_pos)) return alloc_failed("nn", want);
+
+    const float* pos = targets;
+    if (host_in) {
+        if (copy_to_device(device, d_pos, targets, b_pos, s)) return 1;
+        pos = d_pos;
+    } else if (order_after_caller(device, s)) {
+        return 2;
+    }
+    Drain drain{s};
+
+    MQR_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_check_finite, dim3(std::min<unsigned>(nb(3 * n), 4096)), dim3(kT), 0, s, pos, 3 * n,
+                       kCoordLimit, flag);
+    MQR_CHECK_HIP(hipGetLastError());
+    int32_t bad = 0;
+    MQR_CHECK_HIP(hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, s));
+    MQR_CHECK_HIP(hipStreamSynchronize(s));
+    MQR_REQUIRE(!bad, "nn: a target coordinate is not finite or beyond 1e18 in magnitude");
+
+    mqr_nn* h = new mqr_nn();
+    h->device = device;
+    h->n = n;
+    h->P = P;
+    h->depth = ceil_log2(P);
+    const size_t b_box = al256(sizeof(float4) * 2 * P), b_pts = al256(sizeof(float4) * n);
+    if (hipMalloc(&h->mem, 2 * b_box + b_pts + 256) != hipSuccess) {
+        delete h;
+        return alloc_failed("nn", 2 * b_box + b_pts + 256);
+    }
+    char* base = (char*)h->mem;
+    h->lo = (float4*)base;
+    h->hi = (float4*)(base + b_box);
+    h->pts = (float4*)(base + 2 * b_box);
+    h->bb = (uint32_t*)(base + 2 * b_box + b_pts);
+
+    int rc = 0;
+    auto step = [&](hipError_t e) {
+        if (e != hipSuccess && !rc) {
+            set_error(std::string("nn: tree build: ") + hipGetErrorString(e));
+            rc = 1;
+        }
+    };
+    const uint32_t init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
+    const unsigned gn = nb(n);
+    step(hipMemcpyAsync(h->bb, init, sizeof init, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_iota, dim3(gn), dim3(kT), 0, s, ids, n);
+    hipLaunchKernelGGL(k_cm_bounds, dim3(std::min(gn, 4096u)), dim3(256), 0, s, pos, ids, n, h->bb);
+    hipLaunchKernelGGL(k_cm_morton, dim3(gn), dim3(256), 0, s, pos, ids, n, h->bb, keys);
+    step(hipGetLastError());
+    {
+        size_t t2 = tb;
+        step(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint64_t*)keys, keys_s, (const int32_t*)ids, sorted,
+                                                (int)n, 0, 63, s));
+    }
+    hipLaunchKernelGGL(k_cm_leaf_boxes, dim3(nb(P)), dim3(256), 0, s, pos, sorted, n, P, h->lo, h->hi, h->pts);
+    for (int64_t first = P / 2; first >= 1; first /= 2)
+        hipLaunchKernelGGL(k_cm_level, dim3(nb(first)), dim3(256), 0, s, first, first, h->lo, h->hi);
+    step(hipGetLastError());
+    step(hipStreamSynchronize(s));
+    if (rc) {
+        (void)hipFree(h->mem);
+        delete h;
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int mqr_nn_destroy(mqr_nn* h) {
+    if (!h) return 0;
+    (void)hipSetDevice(h->device);
+    (void)hipFree(h->mem);  // waits for the device: nothing still reads the tree
+    delete h;
+    return 0;
+}
+
+int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* dist, int32_t* idx, int out_loc) {
+    MQR_REQUIRE(h, "null argument");
+    MQR_REQUIRE(nq >= 0 && nq < ((int64_t)1 << 31), "nn: too many queries (nq >= 2^31)");
+    if (nq == 0) return 0;
+    MQR_REQUIRE(queries && dist, "null argument");
+    MQR_REQUIRE((loc == MQR_HOST || loc == MQR_DEVICE) && (out_loc == MQR_HOST || out_loc == MQR_DEVICE),
+                "nn: loc and out_loc must be MQR_HOST or MQR_DEVICE");
+    const int device = h->device;
+    MQR_CHECK_HIP(hipSetDevice(device));
+    hipStream_t s = g_streams.get(device);
+    MQR_REQUIRE(s, "nn: no stream for the device");
+    const size_t lds = sizeof(int32_t) * 256 * (size_t)(h->depth + 2);
+    MQR_REQUIRE(lds <= 64 * 1024, "nn: the tree is too deep for the traversal stack");
+
+    size_t tb = 0;
+    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                     (const int32_t*)nullptr, (int32_t*)nullptr, (int)nq, 0, 63, s));
+    const bool host_in = loc == MQR_HOST, host_out = out_loc == MQR_HOST;
+    const size_t b_q = host_in ? sizeof(float) * 3 * nq : 0;
+    const size_t b_d = host_out ? sizeof(double) * nq : 0, b_i = host_out && idx ? sizeof(int32_t) * nq : 0;
+    const size_t want = al256(b_q) + al256(b_d) + al256(b_i) + 256 + 2 * al256(sizeof(uint64_t) * nq) +
+                        2 * al256(sizeof(int32_t) * nq) + al256(tb + 16) + 256;
+    CachedBlock blk(device, want);
+    if (!blk.p) return alloc_failed("nn", want);
+    float* d_q = host_in ? (float*)blk.take(b_q) : nullptr;
+    double* d_d = host_out ? (double*)blk.take(b_d) : nullptr;
+    int32_t* d_i = host_out && idx ? (int32_t*)blk.take(b_i) : nullptr;
+    int32_t* flag = (int32_t*)blk.take(sizeof(int32_t));
+    uint64_t* keys = (uint64_t*)blk.take(sizeof(uint64_t) * nq);
+    uint64_t* keys_s = (uint64_t*)blk.take(sizeof(uint64_t) * nq);
+    int32_t* ids = (int32_t*)blk.take(sizeof(int32_t) * nq);
+    int32_t* order = (int32_t*)blk.take(sizeof(int32_t) * nq);
+    void* tmp = blk.take(tb + 16);
+    if (!flag || !keys || !keys_s || !ids || !order || !tmp || (host_in && !d_q) ||
+        (host_out && (!d_d || (idx && !d_i))))
+        return alloc_failed("nn", want);
+
+    const float* Q = queries;
+    if (host_in) {
+        if (copy_to_device(device, d_q, queries, b_q, s)) return 1;
+        Q = d_q;
+    }
+    if ((!host_in || !host_out) && order_after_caller(device, s)) return 2;
+    Drain drain{s};
+
+    MQR_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
+    hipLaunchKernelGGL(k_check_finite, dim3(std::min<unsigned>(nb(3 * nq), 4096)), dim3(kT), 0, s, Q, 3 * nq,
+                       kCoordLimit, flag);
+    MQR_CHECK_HIP(hipGetLastError());
+    int32_t bad = 0;
+    MQR_CHECK_HIP(hipMemcpyAsync(&bad, flag, sizeof bad, hipMemcpyDeviceToHost, s));
+    MQR_CHECK_HIP(hipStreamSynchronize(s));
+    MQR_REQUIRE(!bad, "nn: a query coordinate is not finite or beyond 1e18 in magnitude");
+
+    // queries in the Morton order of the tree's frame (a query outside the targets' box clamps to its faces)
+    const unsigned gq = nb(nq);
+    hipLaunchKernelGGL(k_iota, dim3(gq), dim3(kT), 0, s, ids, nq);
+    hipLaunchKernelGGL(k_cm_morton, dim3(gq), dim3(256), 0, s, Q, ids, nq, h->bb, keys);
+    MQR_CHECK_HIP(hipGetLastError());
+    {
+        size_t t2 = tb;
+        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint64_t*)keys, keys_s, (const int32_t*)ids,
+                                                         order, (int)nq, 0, 63, s));
+    }
+    double* o_d = host_out ? d_d : dist;
+    int32_t* o_i = host_out ? d_i : idx;
+    hipLaunchKernelGGL(k_nn1, dim3(gq), dim3(256), lds, s, Q, (const int32_t*)order, nq, h->pts, h->n, h->P, h->lo,
+                       h->hi, o_d, o_i);
+    MQR_CHECK_HIP(hipGetLastError());
+    if (host_out) {
+        if (copy_to_host(device, dist, d_d, b_d, s)) return 1;
+        if (idx && copy_to_host(device, idx, d_i, b_i, s)) return 1;
+    }
+    MQR_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int mqr_distance_stats(int device, const double* dist, int64_t n, int loc, double threshold,
+                       mqr_distance_stats_result* out) {
+    MQR_REQUIRE(out && dist, "null argument");
+    MQR_REQUIRE(n > 0, "distance stats: the array is empty");
+    MQR_REQUIRE(n < ((int64_t)1 << 31), "distance stats: too many values (n >= 2^31)");
+    MQR_REQUIRE(loc == MQR_HOST || loc == MQR_DEVICE, "distance stats: loc must be MQR_HOST or MQR_DEVICE");
+    MQR_CHECK_HIP(hipSetDevice(device));
+    hipStream_t s = g_streams.get(device);
+    MQR_REQUIRE(s, "distance stats: no stream for the device");
+
+    size_t tb = 0;
+    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n,
+                                                    0, 63, s));
+    const bool host_in = loc == MQR_HOST;
+    const size_t b_x = host_in ? sizeof(double) * n : 0;
+    const int64_t nblk = nb(n, kTile);
+    const size_t want = al256(b_x) + al256(sizeof(StatsRes)) + al256(sizeof(uint64_t) * n) +
+                        al256(sizeof(double) * kSlab * nblk) + al256(tb + 16) + 256;
+    CachedBlock blk(device, want);
+    if (!blk.p) return alloc_failed("distance stats", want);
+    double* d_x = host_in ? (double*)blk.take(b_x) : nullptr;
+    StatsRes* res = (StatsRes*)blk.take(sizeof(StatsRes));
+    uint64_t* sorted = (uint64_t*)blk.take(sizeof(uint64_t) * n);
+    double* slabs = (double*)blk.take(sizeof(double) * kSlab * nblk);
+    void* tmp = blk.take(tb + 16);
+    if (!res || !sorted || !slabs || !tmp || (host_in && !d_x)) return alloc_failed("distance stats", want);
+
+    const double* x = dist;
+    if (host_in) {
+        if (copy_to_device(device, d_x, dist, b_x, s)) return 1;
+        x = d_x;
+    } else if (order_after_caller(device, s)) {
+        return 2;
+    }
+    Drain drain{s};
+
+    hipLaunchKernelGGL(k_stats<0>, dim3((unsigned)nblk), dim3(kT), 0, s, x, n, threshold, (const double*)nullptr, slabs);
+    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk, res->r0);
+    hipLaunchKernelGGL(k_stats<1>, dim3((unsigned)nblk), dim3(kT), 0, s, x, n, threshold, (const double*)res->r0, slabs);
+    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk, res->r1);
+    MQR_CHECK_HIP(hipGetLastError());
+    {
+        // non-negative doubles order as their bit patterns (the sign bit is clear: 63 key bits)
+        size_t t2 = tb;
+        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, t2, (const uint64_t*)x, sorted, (int)n, 0, 63, s));
+    }
+    hipLaunchKernelGGL(k_median, dim3(1), dim3(64), 0, s, (const uint64_t*)sorted, n, res);
+    MQR_CHECK_HIP(hipGetLastError());
+    StatsRes r;
+    MQR_CHECK_HIP(hipMemcpyAsync(&r, res, sizeof r, hipMemcpyDeviceToHost, s));
+    MQR_CHECK_HIP(hipStreamSynchronize(s));
+
+    mqr_distance_stats_result o{};
+    o.mean = r.r0[0] / (double)n;
+    o.std = std::sqrt(r.r1[0] / (double)n);
+    o.min = r.r0[kNS];
+    o.max = r.r0[kNS + 1];
+    o.median = r.median;
+    o.count_below = (int64_t)r.r0[1];  // exact in float64: < 2^31
+    o.count = n;
+    *out = o;
+    return 0;
+}
+
+int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_t* triangles, int64_t nt, int loc,
+                     mqr_mesh_measure_result* out, mqr_edge_list** boundary) {
+    MQR_REQUIRE(out, "null argument");
+    if (boundary) *boundary = nullptr;
+    MQR_REQUIRE(nv > 0, "mesh measure: the mesh has no vertices");
+    MQR_REQUIRE(nt >= 0 && vertices && (triangles || nt == 0), "null argument");
+    MQR_REQUIRE(loc == MQR_HOST || loc == MQR_DEVICE, "mesh measure: loc must be MQR_HOST or MQR_DEVICE");
+    MQR_REQUIRE(nt < ((int64_t)1 << 31) / 3 && nv < ((int64_t)1 << 31), "mesh measure: mesh too large (3 nt >= 2^31)");
+    MQR_CHECK_HIP(hipSetDevice(device));
+    hipStream_t s = g_streams.get(device);
+    MQR_REQUIRE(s, "mesh measure: no stream for the device");
+
+    const int64_t m = 3 * nt;
+    const int vbits = ceil_log2(nv + 1);
+    const int64_t nblk_t = nb(nt, kTile);
+    size_t tb_e = 0, tb_sel = 0;
+    hipcub::CountingInputIterator<int32_t> it(0);
+    if (nt > 0) {
+        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_e, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                         (const int32_t*)nullptr, (int32_t*)nullptr, (int)m, 0,
+                                                         32 + vbits, s));
+        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb_sel, it, (const uint8_t*)nullptr, (int32_t*)nullptr,
+                                                    (int64_t*)nullptr, (int)m, s));
+    }
+    const size_t tb = std::max(tb_e, tb_sel) + 16;
+    const bool host_in = loc == MQR_HOST;
+    const size_t b_pos = host_in ? sizeof(float) * 3 * nv : 0, b_tri = host_in ? sizeof(int32_t) * m : 0;
+    const int64_t me = std::max<int64_t>(m, 1);  // entries of each edge array (a point cloud still takes one)
+    const size_t want = al256(b_pos) + al256(b_tri) + al256(sizeof(MeasureCtrl)) + al256(sizeof(int32_t) * nv) +
+                        2 * al256(sizeof(uint64_t) * me) + 2 * al256(sizeof(int32_t) * me) + al256(me) +
+                        al256(sizeof(double) * kSlab * nblk_t) + al256(tb) + 256;
+    CachedBlock blk(device, want);
+    if (!blk.p) return alloc_failed("mesh measure", want);
+    float* d_pos = host_in ? (float*)blk.take(b_pos) : nullptr;
+    int32_t* d_tri = host_in && nt > 0 ? (int32_t*)blk.take(b_tri) : nullptr;
+    MeasureCtrl* ctrl = (MeasureCtrl*)blk.take(sizeof(MeasureCtrl));
+    int32_t* vid = (int32_t*)blk.take(sizeof(int32_t) * nv);
+    uint64_t* keys = (uint64_t*)blk.take(sizeof(uint64_t) * me);
+    uint64_t* keys_s = (uint64_t*)blk.take(sizeof(uint64_t) * me);
+    int32_t* slot = (int32_t*)blk.take(sizeof(int32_t) * me);
+    int32_t* slot_s = (int32_t*)blk.take(sizeof(int32_t) * me);
+    uint8_t* bflag = (uint8_t*)blk.take(me);
+    double* slabs = (double*)blk.take(sizeof(double) * kSlab * nblk_t);
+    void* tmp = blk.take(tb);
+    if (!ctrl || !vid || !keys || !keys_s || !slot || !slot_s || !bflag || !slabs || !tmp ||
+        (host_in && (!d_pos || (nt > 0 && !d_tri))))
+        return alloc_failed("mesh measure", want);
+
+    const float* pos = vertices;
+    const int32_t* tri = triangles;
+    if (host_in) {
+        if (copy_to_device(device, d_pos, vertices, b_pos, s) ||
+            (nt > 0 && copy_to_device(device, d_tri, triangles, b_tri, s)))
+            return 1;
+        pos = d_pos, tri = d_tri;
+    } else if (order_after_caller(device, s)) {
+        return 2;
+    }
+    Drain drain{s};
+
+    // ---- checks and bounds (no kernel gathers through an index before the flags are read)
+    MQR_CHECK_HIP(hipMemsetAsync(ctrl, 0, sizeof(MeasureCtrl), s));
+    MQR_CHECK_HIP(hipMemsetAsync(ctrl->bb, 0xff, 3 * sizeof(uint32_t), s));
+    if (nt > 0) hipLaunchKernelGGL(k_check_indices, dim3(nb(m)), dim3(kT), 0, s, tri, m, nv, &ctrl->bad_index);
+    hipLaunchKernelGGL(k_check_finite, dim3(std::min<unsigned>(nb(3 * nv), 4096)), dim3(kT), 0, s, pos, 3 * nv,
+                       FLT_MAX, &ctrl->bad_coord);
+    hipLaunchKernelGGL(k_iota, dim3(nb(nv)), dim3(kT), 0, s, vid, nv);
+    hipLaunchKernelGGL(k_cm_bounds, dim3(std::min<unsigned>(nb(nv), 4096)), dim3(256), 0, s, pos, (const int32_t*)vid,
+                       nv, ctrl->bb);
+    MQR_CHECK_HIP(hipGetLastError());
+    MeasureCtrl hc;
+    MQR_CHECK_HIP(hipMemcpyAsync(&hc, ctrl, sizeof hc, hipMemcpyDeviceToHost, s));
+    MQR_CHECK_HIP(hipStreamSynchronize(s));
+    MQR_REQUIRE(!hc.bad_index, "mesh measure: a triangle index is outside [0, nv)");
+    MQR_REQUIRE(!hc.bad_coord, "mesh measure: a vertex coordinate is not finite");
+
+    mqr_mesh_measure_result r{};
+    for (int a = 0; a < 3; ++a) {
+        r.min_bound[a] = (double)host_from_ordered(hc.bb[a]);
+        r.max_bound[a] = (double)host_from_ordered(hc.bb[3 + a]);
+    }
+    r.num_vertices = nv;
+    r.num_triangles = nt;
+    if (nt == 0) {
+        *out = r;
+        return 0;
+    }
+
+    // ---- area and signed volume
+    hipLaunchKernelGGL(k_tri_measure, dim3((unsigned)nblk_t), dim3(kT), 0, s, pos, tri, nt, slabs);
+    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk_t, ctrl->sums);
+    // ---- the edge runs: boundary slots, closed and oriented
+    hipLaunchKernelGGL(k_edge_keys<false>, dim3(nb(m)), dim3(kT), 0, s, tri, nt, (uint64_t)0, keys, slot);
+    MQR_CHECK_HIP(hipGetLastError());
+    {
+        size_t t2 = tb;
+        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint64_t*)keys, keys_s, (const int32_t*)slot,
+                                                         slot_s, (int)m, 0, 32 + vbits, s));
+    }
+    MQR_CHECK_HIP(hipMemsetAsync(bflag, 0, m, s));
+    hipLaunchKernelGGL(k_edge_runs, dim3(nb(m)), dim3(kT), 0, s, (const uint64_t*)keys_s, (const int32_t*)slot_s, m, tri,
+                       bflag, ctrl);
+    MQR_CHECK_HIP(hipGetLastError());
+    {
+        // boundary slots ascending (the unsorted slot array is free again: the compacted list goes there)
+        size_t t2 = tb;
+        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(tmp, t2, it, (const uint8_t*)bflag, slot, &ctrl->nboundary, (int)m, s));
+    }
+    MQR_CHECK_HIP(hipMemcpyAsync(&hc, ctrl, sizeof hc, hipMemcpyDeviceToHost, s));
+    MQR_CHECK_HIP(hipStreamSynchronize(s));
+
+    r.surface_area = hc.sums[0];
+    r.is_closed_oriented = hc.open ? 0 : 1;
+    r.volume = hc.open ? 0.0 : std::fabs(hc.sums[1]);
+    r.boundary_edges = hc.nboundary;
+    if (boundary && hc.nboundary > 0) {
+        mqr_edge_list* e = new mqr_edge_list();
+        e->device = device;
+        e->n = hc.nboundary;
+        if (hipMalloc((void**)&e->pairs, sizeof(int32_t) * 2 * e->n) != hipSuccess) {
+            delete e;
+            return alloc_failed("mesh measure", sizeof(int32_t) * 2 * (size_t)hc.nboundary);
+        }
+        hipLaunchKernelGGL(k_boundary_pairs, dim3(nb(e->n)), dim3(kT), 0, s, (const int32_t*)slot, e->n, tri, e->pairs);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+            (void)hipFree(e->pairs);
+            delete e;
+            set_error("mesh measure: the boundary list kernel failed");
+            return 1;
+        }
+        *boundary = e;
+    }
+    *out = r;
+    return 0;
+}
+
+int mqr_edge_list_count(mqr_edge_list* list, int64_t* n) {
+    MQR_REQUIRE(n, "null argument");
+    *n = list ? list->n : 0;
+    return 0;
+}
+
+int mqr_edge_list_copy(mqr_edge_list* list, int32_t* pairs, int loc) {
+    if (!list || list->n == 0) return 0;
+    MQR_REQUIRE(pairs, "null argument");
+    MQR_REQUIRE(loc == MQR_HOST || loc == MQR_DEVICE, "edge list: loc must be MQR_HOST or MQR_DEVICE");
+    MQR_CHECK_HIP(hipSetDevice(list->device));
+    hipStream_t s = g_streams.get(list->device);
+    MQR_REQUIRE(s, "edge list: no stream for the device");
+    const size_t bytes = sizeof(int32_t) * 2 * list->n;
+    if (loc == MQR_HOST) return copy_to_host(list->device, pairs, list->pairs, bytes, s);
+    if (order_after_caller(list->device, s)) return 2;
+    MQR_CHECK_HIP(hipMemcpyAsync(pairs, list->pairs, bytes, hipMemcpyDeviceToDevice, s));
+    MQR_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int mqr_edge_list_free(mqr_edge_list* list) {
+    if (!list) return 0;
+    (void)hipSetDevice(list->device);
+    (void)hipFree(list->pairs);
+    delete list;
+    return 0;
+}
+
+}  // extern "C"

@@ -137,6 +137,15 @@ SIGNATURES = {
                                                   ctypes.c_int, ctypes.c_int64, ctypes.POINTER(_vp), _i64p]),
     "mqr_mesh_quality": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, ctypes.c_int,
                                         _vp]),
+    "mqr_nn_create": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "mqr_nn_query": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int]),
+    "mqr_nn_destroy": (ctypes.c_int, [_vp]),
+    "mqr_distance_stats": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double, _vp]),
+    "mqr_mesh_measure": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, _vp,
+                                        ctypes.POINTER(_vp)]),
+    "mqr_edge_list_count": (ctypes.c_int, [_vp, _i64p]),
+    "mqr_edge_list_copy": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "mqr_edge_list_free": (ctypes.c_int, [_vp]),
     "mqr_vbg_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_vbg_set_variant": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_check_div64": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
@@ -269,6 +278,7 @@ ORDERED = frozenset({
     "mqr_mesh_filter_components", "mqr_mesh_quality", "mqr_memcpy",
     "mqr_cloudset_create", "mqr_cloudset_voxel_down", "mqr_evaluate_pairs", "mqr_icp_pairs", "mqr_information_pairs",
     "mqr_odometry_information_pairs", "mqr_colormap_create", "mqr_colormap_colors",
+    "mqr_nn_create", "mqr_nn_query", "mqr_distance_stats", "mqr_mesh_measure", "mqr_edge_list_copy",
 })
 _tls = threading.local()
 

@@ -36,8 +36,13 @@ def _pinhole_params(K, T):
         inv = np.array([[1.0 / K[0, 0], 0.0, -K[0, 2] / K[0, 0]],
                         [0.0, 1.0 / K[1, 1], -K[1, 2] / K[1, 1]],
                         [0.0, 0.0, 1.0]])
-    else:
-        inv = np.linalg.inv(K)
+    else:  # the adjugate over the determinant, operation by operation as csrc/raycast.hip's pinhole()
+        a, b, c, d, e, f, g, h, i = (float(x) for x in K.reshape(9))
+        A, B, C = e * i - f * h, -(d * i - f * g), d * h - e * g
+        det = a * A + b * B + c * C
+        inv = np.array([[A, -(b * i - c * h), b * f - c * e],
+                        [B, a * i - c * g, -(a * f - c * d)],
+                        [C, -(a * h - b * g), a * e - b * d]]) / det
     RT = T[:3, :3].T
     m = np.empty((3, 3))
     for r in range(3):

@@ -1,7 +1,8 @@
 """Ray casting (row f1: RaycastingScene for colour-aligned depth) vs the brute-force float64
 oracle (oracle/mqr_oracle.c orc_raycast).  Parity against Embree itself is unpinned (Open3D is
 not installed here); the bar: hit/miss agreement >= 99.9 % of rays, |dt| <= 1e-5 * t on common
-hits, the fused pinhole path bit-identical to create_rays_pinhole + cast_rays."""
+hits, the fused pinhole path bit-identical to create_rays_pinhole + cast_rays.  The exact cases (edges,
+vertices, axis-parallel rays, ties, duplicate Morton keys, deep trees) are in test_gpu_raycast_cases.py."""
 import numpy as np
 import pytest
 

@@ -268,6 +268,35 @@ int mqr_decode_depth_masked(int device, const float* raw, int raw_loc, int N, in
                             const double* fars, const uint8_t* strong, const uint8_t* mask, const uint8_t* has_mask,
                             int mask_loc, float* depth_out, int out_loc, uint8_t* frame_ok);
 
+/* Device-side colour-frame ingestion (csrc/colorframes.hip).  N raw Quest camera frames (Android
+ * YUV_420_888, raw_loc MQR_HOST / MQR_DEVICE, frame f at raw + f * frame_stride; the stride and the bases
+ * need no alignment) -> rgb_out[N][H][W][3] uint8 (out_loc), R,G,B per pixel, or B,G,R when bgr != 0.
+ * Replaces convert_yuv420_888_to_bgr (scripts/utils/image_utils.py:6-71) per frame; the colour arithmetic
+ * restates OpenCV's as recalled (csrc/color_convert.hpp: parity unpinned).  W and H are even.  The plane
+ * layout is resolved by the caller (mqr/colorframes.py resolve_layout): byte (row, col) of a plane is at
+ * base + row * row_stride + col * step of its frame; Y has H x W of them, U and V H/2 x W/2.  Every such byte
+ * must lie below valid_bytes (checked before launch; nothing past it is read).
+ * Optional per-frame statistics of the decoded image, host arrays, computed only when non-null:
+ *   hist[N][256]     exact histogram of the blue channel;
+ *   lap_sums[N][2]   the exact sums of x and of x*x over the 3x3 Laplacian (ksize 1, border reflect-101) of
+ *                    the integer grey image. */
+typedef struct mqr_yuv_layout {
+    int64_t y_base, y_row_stride, y_pixel_stride;
+    int64_t u_base, u_row_stride, u_step;
+    int64_t v_base, v_row_stride, v_step;
+    int64_t valid_bytes;
+} mqr_yuv_layout;
+int mqr_decode_color_frames(int device, const uint8_t* raw, int raw_loc, int N, int64_t frame_stride, int W, int H,
+                            const mqr_yuv_layout* layout, int bgr, uint8_t* rgb_out, int out_loc, uint32_t* hist,
+                            int64_t* lap_sums);
+/* Device time of the last completed mqr_decode_color_frames call on `device`, from events around its
+ * kernels: the decode kernel, and the statistics pass with its memset (0 when no statistics were asked for). */
+int mqr_color_frames_last_ms(int device, float* decode_ms, float* stats_ms);
+/* The integer constants of that arithmetic, in the order CY, CUB, CUG, CVG, CVR, shift, grey B, grey G,
+ * grey R, grey shift (csrc/color_convert.hpp is their one home; the host path reads them from here). */
+#define MQR_COLOR_CONSTANTS 10
+int mqr_color_constants(int32_t* out, int n);
+
 /* Host reads of the drop-in integrate.  Replaces, for n frames, the raw depth
  * read of DepthDataIO.load_depth_map (np.fromfile of H*W little-endian float32,
  * scripts/dataio/depth_data_io.py:33-53) and load_confidence_map (np.load of the np.savez npz:

@@ -116,6 +116,11 @@ SIGNATURES = {
     "mqr_decode_depth_masked": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, _f64p, _f64p, _u8p, _vp, _u8p, ctypes.c_int, _vp,
                                                ctypes.c_int, _u8p]),
+    "mqr_decode_color_frames": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                               ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int,
+                                               _vp, _vp]),
+    "mqr_color_constants": (ctypes.c_int, [_i32p, ctypes.c_int]),
+    "mqr_color_frames_last_ms": (ctypes.c_int, [ctypes.c_int, _f32p, _f32p]),
     "mqr_color_vertices": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _f64p, ctypes.c_double,
                                           ctypes.c_double, ctypes.c_int, _vp, _vp, ctypes.c_int]),
@@ -273,6 +278,7 @@ ORDERED = frozenset({
     "mqr_touch", "mqr_integrate", "mqr_integrate_frames", "mqr_vbg_export", "mqr_vbg_import",
     "mqr_vbg_pack_weighted", "mqr_vbg_unpack_weighted", "mqr_xchg_create", "mqr_xchg_send_segment",
     "mqr_xchg_recv_segment", "mqr_geom_copy", "mqr_confidence", "mqr_confidence_counts", "mqr_decode_depth", "mqr_decode_depth_masked",
+    "mqr_decode_color_frames",
     "mqr_color_vertices",
     "mqr_color_map", "mqr_scene_add_triangles", "mqr_scene_cast_pinhole", "mqr_scene_cast_rays",
     "mqr_mesh_filter_components", "mqr_mesh_quality", "mqr_memcpy",

@@ -48,6 +48,53 @@ KNN = 3
 DEPTH_TRUNC = 3.0
 
 
+def _resident_images(images, t_hit, device, keep):
+    """The (N,H,W,3) uint8 keyframes and their (N,H,W) float32 depths as one pair of pointers in one place
+    (the C ABI takes a single location for both): images or t_hit already in HBM on `device` (detected
+    with mqr.geometry.device_ptr) are used in place and the other goes up beside them; both on the host
+    stay there.  -> (N, H, W, image pointer, depth pointer, location); `keep` collects what must outlive
+    the call."""
+    from .geometry import device_ptr
+    from ._lib import MQR_DEVICE, DeviceBuffer
+    di = device_ptr(images, device) if getattr(images, "dtype", None) == np.uint8 else None
+    if di is not None:
+        shape = tuple(images.shape)
+        if len(shape) != 4 or shape[3] != 3:
+            raise ValueError(f"images must be (N,H,W,3) uint8, got {shape}")
+        im = None
+    else:
+        im = np.ascontiguousarray(images.numpy() if hasattr(images, "numpy") else images, dtype=np.uint8)
+        if im.ndim != 4 or im.shape[3] != 3:
+            raise ValueError(f"images must be (N,H,W,3) uint8, got {im.shape}")
+        shape = im.shape
+    N, H, W = (int(x) for x in shape[:3])
+    dt = device_ptr(t_hit, device) if getattr(t_hit, "dtype", None) == np.float32 else None
+    tshape = tuple(t_hit.shape) if hasattr(t_hit, "shape") else np.shape(t_hit)
+    if int(np.prod(tshape)) != N * H * W:
+        raise ValueError(f"t_hit must be ({N},{H},{W}) float32, got {tshape}")
+    if N == 0 or (di is None and dt is None):
+        if im is None:
+            im = np.ascontiguousarray(images.numpy(), dtype=np.uint8)
+        d = np.ascontiguousarray(t_hit.numpy() if dt is not None else t_hit, dtype=np.float32).reshape(N, H, W)
+        keep += [im, d]
+        return N, H, W, ptr(im), ptr(d), MQR_HOST
+    if di is not None:
+        keep.append(images)
+        iptr = ctypes.c_void_p(di[0])
+    else:  # images go up beside the resident depths
+        buf = DeviceBuffer.from_array(im, int(device))
+        keep.append(buf)
+        iptr = buf.ptr
+    if dt is not None:
+        keep.append(t_hit)
+        tptr = ctypes.c_void_p(dt[0])
+    else:
+        buf = DeviceBuffer.from_array(np.ascontiguousarray(t_hit, dtype=np.float32).reshape(N, H, W), int(device))
+        keep.append(buf)
+        tptr = buf.ptr
+    return N, H, W, iptr, tptr, MQR_DEVICE
+
+
 def color_vertices(vertices, images, depths, K, T_wc, max_depth=MAX_DEPTH,
                    visibility_threshold=VISIBILITY_THRESHOLD, margin=MARGIN, device=0):
     """vertices (V,3) float32; images (N,H,W,3) uint8 RGB; depths (N,H,W) float32 colour-aligned
@@ -76,27 +123,17 @@ def color_map(vertices, images, t_hit, K, T_wc, max_depth=MAX_DEPTH, visibility_
     keyframes' raycast_in_color_view depth (inf on a miss).  Returns (colours (V,3) float32,
     counts (V,) int32 = keyframes averaged; 0 where the colour comes from the knn fill).  Vertices and
     t_hit already in HBM on `device` (a mesh from this package's extraction, a cast's t_hit Tensor) are
-    used in place."""
+    used in place, and so are images held there."""
     from .geometry import device_ptr
-    from ._lib import MQR_DEVICE, DeviceBuffer
-    im = np.ascontiguousarray(images, dtype=np.uint8)
-    if im.ndim != 4 or im.shape[3] != 3:
-        raise ValueError(f"images must be (N,H,W,3) uint8, got {im.shape}")
-    N, H, W = im.shape[:3]
+    from ._lib import MQR_DEVICE
+    keep = []
+    N, H, W, iptr, tptr, iloc = _resident_images(images, t_hit, device, keep)
     dv = device_ptr(vertices, device) if getattr(vertices, "dtype", None) == np.float32 else None
     if dv is not None and vertices.shape[-1:] == (3,):
         nv, vptr, vloc = int(np.prod(vertices.shape[:-1])), ctypes.c_void_p(dv[0]), MQR_DEVICE
     else:
         V = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         nv, vptr, vloc = len(V), ptr(V), MQR_HOST
-    dt = device_ptr(t_hit, device) if getattr(t_hit, "dtype", None) == np.float32 else None
-    keep = None
-    if dt is not None and int(np.prod(t_hit.shape)) == N * H * W:  # images go up beside the resident depths
-        keep = DeviceBuffer.from_array(im, int(device))
-        iptr, tptr, iloc = keep.ptr, ctypes.c_void_p(dt[0]), MQR_DEVICE
-    else:
-        d = np.ascontiguousarray(t_hit, dtype=np.float32).reshape(N, H, W)
-        iptr, tptr, iloc = ptr(im), ptr(d), MQR_HOST
     Kd = np.ascontiguousarray(K, dtype=np.float64).reshape(N, 9)
     Td = np.ascontiguousarray(T_wc, dtype=np.float64).reshape(N, 16)
     out = np.empty((nv, 3), np.float32)
@@ -157,25 +194,23 @@ class ColorMapOptimizer:
 
     vertices (V,3) float32 (or a device mesh's positions), images (N,H,W,3) uint8, t_hit (N,H,W) float32
     colour-aligned depth, K (N,3,3), T_wc (N,4,4) world->camera.  Builds the utility images, the
-    depth-boundary masks and both visibility lists at T_wc; vertices / t_hit already in HBM on `device`
-    are used in place (the vertices must outlive the optimiser)."""
+    depth-boundary masks and both visibility lists at T_wc; vertices / images / t_hit already in HBM on
+    `device` (e.g. the images mqr.colorframes.decode_color_frames wrote through out_ptr, wrapped in a device
+    Tensor) are used in place (the vertices must outlive the optimiser)."""
 
     def __init__(self, vertices, images, t_hit, K, T_wc, option=None, depth_trunc=DEPTH_TRUNC, device=0):
         from .geometry import device_ptr
-        from ._lib import MQR_DEVICE, DeviceBuffer
+        from ._lib import MQR_DEVICE
         opt = option if option is not None else RigidOptimizerOption()
         self.option, self.device, self._h = opt, int(device), None
-        im = np.ascontiguousarray(images, dtype=np.uint8)
-        if im.ndim != 4 or im.shape[3] != 3:
-            raise ValueError(f"images must be (N,H,W,3) uint8, got {im.shape}")
-        N, H, W = im.shape[:3]
+        self._keep = [vertices]
+        N, H, W, iptr, tptr, iloc = _resident_images(images, t_hit, device, self._keep)
         Kd = np.ascontiguousarray(K, dtype=np.float64)
         Td = np.ascontiguousarray(T_wc, dtype=np.float64)
         if Kd.size != 9 * N or Td.size != 16 * N:
             raise ValueError(f"K must be ({N},3,3) and T_wc ({N},4,4), got {Kd.shape} and {Td.shape}")
         Kd, Td = Kd.reshape(N, 9), Td.reshape(N, 16)
         dv = device_ptr(vertices, device) if getattr(vertices, "dtype", None) == np.float32 else None
-        self._keep = [vertices]
         if dv is not None and vertices.shape[-1:] == (3,):
             nv, vptr, vloc = int(np.prod(vertices.shape[:-1])), ctypes.c_void_p(dv[0]), MQR_DEVICE
         else:
@@ -183,17 +218,6 @@ class ColorMapOptimizer:
             if V.ndim != 2 or V.shape[1] != 3:
                 raise ValueError(f"vertices must be (V,3) float32, got {V.shape}")
             nv, vptr, vloc = len(V), ptr(V), MQR_HOST
-        dt = device_ptr(t_hit, device) if getattr(t_hit, "dtype", None) == np.float32 else None
-        tshape = tuple(t_hit.shape) if hasattr(t_hit, "shape") else np.shape(t_hit)
-        if int(np.prod(tshape)) != N * H * W:
-            raise ValueError(f"t_hit must be ({N},{H},{W}) float32, got {tshape}")
-        if dt is not None and N > 0:  # images go up beside the resident depths, and stay for the colours
-            buf = DeviceBuffer.from_array(im, int(device))
-            self._keep.append(buf)
-            iptr, tptr, iloc = buf.ptr, ctypes.c_void_p(dt[0]), MQR_DEVICE
-        else:
-            d = np.ascontiguousarray(t_hit.numpy() if dt is not None else t_hit, dtype=np.float32).reshape(N, H, W)
-            iptr, tptr, iloc = ptr(im), ptr(d), MQR_HOST
         self.nv, self.N, self.H, self.W = nv, N, H, W
         self._T0 = Td.reshape(N, 4, 4).copy()
         h = ctypes.c_void_p()

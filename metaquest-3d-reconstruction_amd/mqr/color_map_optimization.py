@@ -43,8 +43,9 @@ def _filter_colored(mesh, colors, min_triangle_count):
 
 def optimize_color_pose(vbg, data_io, config, sides=None):
     """-> (colored_mesh, {side: color_dataset}).  `data_io.color` needs load_color_dataset(side=,
-    use_cache=) and load_rgb(side=, timestamp=) (the reference's DataIO has both); `config` the fields of
-    the reference's ColorOptimizationConfig.  `sides`: the Side members to walk (default: this package's
+    use_cache=) and load_rgb(side=, timestamp=) (the reference's DataIO has both); where it also has
+    load_rgb_batch(side, timestamps, device=) (mqr.dataio.ImageDataIO), each side's frames come from one
+    call of that; `config` the fields of the reference's ColorOptimizationConfig.  `sides`: the Side members to walk (default: this package's
     Side enum, in order).  Keyframes of differing sizes raise ValueError."""
     mesh = vbg.extract_triangle_mesh(weight_threshold=config.weight_threshold,
                                      estimated_vertex_number=config.estimated_vertex_number)
@@ -70,8 +71,15 @@ def optimize_color_pose(vbg, data_io, config, sides=None):
         K, T = dataset_intrinsics_extrinsics(color_dataset)
         Ks.append(K)
         Ts.append(T)
-        for i in range(len(color_dataset.timestamps)):
-            rgb = np.asarray(data_io.color.load_rgb(side=side, timestamp=color_dataset.timestamps[i]))
+        n = len(color_dataset.timestamps)
+        if hasattr(data_io.color, "load_rgb_batch"):  # one batched read (raw frames decoded on the device)
+            batch = np.asarray(data_io.color.load_rgb_batch(side, color_dataset.timestamps, device=device)) if n else ()
+            if n and (batch.ndim != 4 or len(batch) != n):
+                raise ValueError(f"load_rgb_batch must return ({n},H,W,3) uint8, got {batch.shape}")
+        else:
+            batch = (np.asarray(data_io.color.load_rgb(side=side, timestamp=color_dataset.timestamps[i]))
+                     for i in range(n))
+        for i, rgb in enumerate(batch):
             if rgb.ndim != 3 or rgb.shape[2] != 3:
                 raise ValueError(f"load_rgb must return (H,W,3) uint8, got {rgb.shape}")
             if (rgb.shape[1], rgb.shape[0]) != (int(color_dataset.widths[i]), int(color_dataset.heights[i])):

@@ -1,4 +1,5 @@
-"""Capture-directory access for the fusion path (Quest layout).
+"""Capture-directory access (Quest layout): the depth side for the fusion path, and the colour side
+(ColorPaths, ImageDataIO, PoseInterpolator below; raw camera frames are decoded by mqr.colorframes).
 
 Mirror of the reference's ``DepthDataIO`` (scripts/dataio/depth_data_io.py:14-261) and of the
 path layout in ``config/project_path_config.py:39-61, 148-196``:
@@ -154,3 +155,331 @@ class DepthDataIO:
         path = self.paths.confidence_path(side, timestamp)
         path.parent.mkdir(parents=True, exist_ok=True)
         np.savez(path, confidence_map=confidence_map.confidence_map, valid_count=confidence_map.valid_count)
+
+
+# ======================================================================================= colour side
+class ColorPaths:
+    """The camera paths of the reference's ImagePathConfig (config/project_path_config.py:6-36, 84-127),
+    under its method names:
+
+        <project>/left_camera_raw/<timestamp>.yuv        raw YUV_420_888 frame
+        <project>/left_camera_rgb/<timestamp>.png        converted frame
+        <project>/left_camera_image_format.json          width, height, planes, base time
+        <project>/left_camera_characteristics.json       intrinsics and the camera's pose on the headset
+        <project>/hmd_poses.csv                          headset poses
+        <project>/dataset/left_camera_dataset[_optimized].npz
+    """
+
+    def __init__(self, project_dir: Path):
+        self.project_dir = Path(project_dir).resolve()
+
+    def get_yuv_dir(self, side: Side) -> Path:
+        return self.project_dir / f"{side.value}_camera_raw"
+
+    def get_yuv_image_paths(self, side: Side) -> list:
+        return sorted(self.get_yuv_dir(side).glob("*.yuv"))
+
+    def get_rgb_dir(self, side: Side) -> Path:
+        return self.project_dir / f"{side.value}_camera_rgb"
+
+    def get_rgb_file_path(self, side: Side, timestamp: int) -> Path:
+        return self.get_rgb_dir(side) / f"{timestamp}.png"
+
+    def get_rgb_image_paths(self, side: Side) -> list:
+        return sorted(self.get_rgb_dir(side).glob("*.png"))
+
+    def get_camera_characteristic_json_path(self, side: Side) -> Path:
+        return self.project_dir / f"{side.value}_camera_characteristics.json"
+
+    def get_camera_format_format_json_path(self, side: Side) -> Path:
+        return self.project_dir / f"{side.value}_camera_image_format.json"
+
+    def get_hmd_pose_csv_path(self) -> Path:
+        return self.project_dir / "hmd_poses.csv"
+
+    def get_color_dataset_path(self, side: Side) -> Path:
+        return self.project_dir / "dataset" / f"{side.value}_camera_dataset.npz"
+
+    def get_optimized_color_dataset_path(self, side: Side) -> Path:
+        return self.project_dir / "dataset" / f"{side.value}_camera_dataset_optimized.npz"
+
+    def get_relative_path(self, path: Path) -> Path:
+        return path.relative_to(self.project_dir)
+
+
+class PoseInterpolator:
+    """Headset pose at a camera timestamp (dataio/helpers/pose_interpolator.py): the nearest pose rows
+    before and after it within 30 ms, linearly / spherically interpolated; one of them alone when the
+    other is missing; None when neither is there.  The same pandas calls as the reference, so bad CSV
+    lines, rows with gaps and duplicate times are treated alike."""
+
+    def __init__(self, pose_csv_path: Path):
+        self.pose_csv_path = pose_csv_path
+        self._df = None
+
+    @property
+    def hmd_pose_df(self):
+        if self._df is None:
+            import pandas as pd
+            df = pd.read_csv(self.pose_csv_path, on_bad_lines="skip").dropna()
+            self._df = df.sort_values("unix_time").reset_index(drop=True)
+        return self._df
+
+    def find_nearest_frames(self, timestamp: int, window_ms: int = 30):
+        window = window_ms * 1000
+        df = self.hmd_pose_df
+        before = df[df["unix_time"] <= timestamp]
+        after = df[df["unix_time"] >= timestamp]
+        prev = before.iloc[-1] if not before.empty and abs(timestamp - before.iloc[-1]["unix_time"]) <= window else None
+        nxt = after.iloc[0] if not after.empty and abs(after.iloc[0]["unix_time"] - timestamp) <= window else None
+        return prev, nxt
+
+    def interpolate_pose(self, timestamp: int):
+        from scipy.spatial.transform import Rotation, Slerp
+        prev, nxt = self.find_nearest_frames(timestamp)
+        if prev is None and nxt is None:
+            return None
+
+        def pos(r):
+            return np.array([r["pos_x"], r["pos_y"], r["pos_z"]])
+
+        def rot(r):
+            return np.array([r["rot_x"], r["rot_y"], r["rot_z"], r["rot_w"]])
+
+        if prev is None:
+            return pos(nxt), rot(nxt)
+        if nxt is None:
+            return pos(prev), rot(prev)
+        t0, t1 = prev["unix_time"], nxt["unix_time"]
+        alpha = (timestamp - t0) / (t1 - t0) if t1 != t0 else 0.0
+        rots = Rotation.from_quat([list(rot(prev)), list(rot(nxt))])
+        return (1 - alpha) * pos(prev) + alpha * pos(nxt), Slerp([0, 1], rots)(alpha).as_quat()
+
+
+class ImageDataIO:
+    """The reference's ImageDataIO (scripts/dataio/image_data_io.py) without OpenCV: PNGs go through Pillow
+    (mqr.colorframes.read_png / write_png), raw frames through mqr.colorframes.  `project_dir`: the capture
+    directory, or a path object with ColorPaths' methods (the reference's ImagePathConfig)."""
+
+    def __init__(self, project_dir):
+        self.image_path_config = project_dir if hasattr(project_dir, "get_yuv_dir") else ColorPaths(project_dir)
+        self.paths = self.image_path_config
+        self._format_info: dict = {}
+
+    # -- timestamps ------------------------------------------------------------------------
+    def _parse_timestamp_stem(self, stem: str, filename: str, prefix: str) -> Optional[int]:
+        if stem.startswith("._"):  # macOS resource-fork sidecar
+            stem = stem[2:]
+        elif stem.startswith("_"):
+            stem = stem.lstrip("_")
+        if stem == "" or not stem.isdigit():
+            print(f"[Warning] Skipping non-timestamped {prefix} file: {filename}")
+            return None
+        return int(stem)
+
+    def _timestamps(self, paths, prefix: str) -> list:
+        out = []
+        for p in paths:
+            ts = self._parse_timestamp_stem(p.stem, p.name, prefix=prefix)
+            if ts is not None:
+                out.append(ts)
+        return out
+
+    def get_yuv_timestamps(self, side: Side) -> list:
+        return self._timestamps(self.image_path_config.get_yuv_image_paths(side=side), "YUV")
+
+    def get_rgb_timestamps(self, side: Side) -> list:
+        return self._timestamps(self.image_path_config.get_rgb_image_paths(side=side), "RGB")
+
+    # -- frames ----------------------------------------------------------------------------
+    def _yuv_path(self, side: Side, timestamp: int) -> Path:
+        return self.image_path_config.get_yuv_dir(side=side) / f"{timestamp}.yuv"
+
+    def load_yuv(self, side: Side, timestamp: int) -> np.ndarray:
+        return np.fromfile(self._yuv_path(side, timestamp), dtype=np.uint8)
+
+    def _cached_format_info(self, side: Side):
+        if side not in self._format_info:
+            self._format_info[side] = self.load_image_format_info(side)
+        return self._format_info[side]
+
+    def load_rgb(self, side: Side, timestamp: int) -> np.ndarray:
+        """(H,W,3) uint8 RGB: the PNG, or -- where there is none and the raw frame is there -- the raw
+        frame converted on the host."""
+        from . import colorframes
+        path = self.image_path_config.get_rgb_file_path(side=side, timestamp=timestamp)
+        if not path.exists() and self._yuv_path(side, timestamp).exists():
+            bgr = colorframes.convert_yuv420_888_to_bgr(self.load_yuv(side, timestamp), self._cached_format_info(side))
+            return np.ascontiguousarray(bgr[..., ::-1])
+        return colorframes.read_png(path)
+
+    def load_rgb_batch(self, side: Side, timestamps, device=None) -> np.ndarray:
+        """(N,H,W,3) uint8 RGB frames of `timestamps`, in order: PNGs where they exist, the others decoded
+        from their raw frames in one batch on `device` (default 0).  FileNotFoundError for a timestamp
+        with neither; ValueError when the frames differ in size."""
+        from . import colorframes
+        from ._io import io_pool
+        timestamps = [int(t) for t in timestamps]
+        cfg = self.image_path_config
+        raw_idx = [i for i, ts in enumerate(timestamps)
+                   if not cfg.get_rgb_file_path(side=side, timestamp=ts).exists()]
+        for i in raw_idx:
+            if not self._yuv_path(side, timestamps[i]).exists():
+                raise FileNotFoundError(f"Image file not found or cannot be read: "
+                                        f"{cfg.get_rgb_file_path(side=side, timestamp=timestamps[i])}")
+        frames: list = [None] * len(timestamps)
+        raw_set = set(raw_idx)
+        png_idx = [i for i in range(len(timestamps)) if i not in raw_set]
+        for i, im in zip(png_idx, io_pool().map(lambda i: colorframes.read_png(
+                cfg.get_rgb_file_path(side=side, timestamp=timestamps[i])), png_idx)):
+            frames[i] = im
+        if raw_idx:
+            raws = list(io_pool().map(lambda i: self.load_yuv(side, timestamps[i]), raw_idx))
+            rgb = colorframes.decode_color_frames(raws, self._cached_format_info(side), order="rgb",
+                                                  device=0 if device is None else int(device))
+            for k, i in enumerate(raw_idx):
+                frames[i] = rgb[k]
+        if len({f.shape for f in frames}) > 1:
+            raise ValueError(f"colour frames of differing sizes: {sorted({f.shape[:2] for f in frames})}")
+        if not frames:
+            return np.zeros((0, 0, 0, 3), np.uint8)
+        return np.stack(frames)
+
+    def save_rgb(self, rgb: np.ndarray, side: Side, timestamp: int):
+        from . import colorframes
+        path = self.image_path_config.get_rgb_file_path(side=side, timestamp=timestamp)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        colorframes.write_png(path, rgb)
+
+    def save_bgr(self, bgr: np.ndarray, side: Side, timestamp: int):
+        self.save_rgb(rgb=np.asarray(bgr)[..., ::-1], side=side, timestamp=timestamp)
+
+    # -- records ---------------------------------------------------------------------------
+    def load_image_format_info(self, side: Side):
+        import json
+        from .models import BaseTime, ImageFormatInfo, ImagePlaneInfo
+        with open(self.image_path_config.get_camera_format_format_json_path(side)) as f:
+            d = json.load(f)
+        planes = [ImagePlaneInfo(buffer_size=p["bufferSize"], row_stride=p["rowStride"], pixel_stride=p["pixelStride"])
+                  for p in d["planes"]]
+        base = d["baseTime"]
+        # (the reference stores baseUnixTimeMs in the field it calls unix_time_ns)
+        return ImageFormatInfo(width=d["width"], height=d["height"], format=d["format"], planes=planes,
+                               base_time=BaseTime(mono_time_ns=base["baseMonoTimeNs"],
+                                                  unix_time_ns=base["baseUnixTimeMs"]))
+
+    def load_camera_characteristics(self, side: Side):
+        import json
+        from scipy.spatial.transform import Rotation
+        from .models import CameraCharacteristics
+        cfg = self.image_path_config
+        path = cfg.get_camera_characteristic_json_path(side)
+        if not path.exists():  # reuse the other side's rather than fail
+            other = Side.LEFT if side == Side.RIGHT else Side.RIGHT
+            fallback = cfg.get_camera_characteristic_json_path(other)
+            if not fallback.exists():
+                raise FileNotFoundError(f"Camera characteristics JSON not found for {side.name} at {path} "
+                                        f"and fallback {fallback} is also missing.")
+            print(f"[Warning] Camera characteristics for {side.name} not found at {path}. "
+                  f"Using {other.name} camera characteristics from {fallback} as a fallback.")
+            path = fallback
+        with open(path, "r", encoding="utf-8") as f:
+            c = json.load(f)
+        size = c["sensor"]["activeArraySize"]
+        k = c["intrinsics"]
+        transl = c["pose"]["translation"]
+        transl[2] *= -1
+        if len(transl) < 3:
+            transl = np.array((0, 0, 0))
+        q = c["pose"]["rotation"]
+        if len(q) >= 4:
+            rot = Rotation.from_quat((-q[0], -q[1], q[2], q[3])).inv()
+            rot *= Rotation.from_euler("x", np.pi)  # Android camera pose -> headset world convention
+            q = rot.as_quat()
+        else:
+            q = np.array((0, 0, 0, 1))
+        return CameraCharacteristics(width=size["right"] - size["left"], height=size["bottom"] - size["top"],
+                                     fx=k["fx"], fy=k["fy"], cx=k["cx"], cy=k["cy"], transl=transl, rot_quat=q)
+
+    def load_hmd_poses(self):
+        import pandas as pd
+        path = self.image_path_config.get_hmd_pose_csv_path()
+        if not path.exists():
+            raise FileNotFoundError(f"HMD poses CSV file not found at {path}")
+        return pd.read_csv(path)
+
+    # -- datasets --------------------------------------------------------------------------
+    def load_color_dataset(self, side: Side, use_cache: bool = True):
+        from .models import CameraDataset
+        path = self.image_path_config.get_color_dataset_path(side=side)
+        if use_cache and path.exists():
+            print(f"[Info] Loading cached color dataset for {side.name} from {path} ...")
+            try:
+                return CameraDataset.load(path)
+            except Exception as e:
+                print(f"[Error] Color dataset cache is corrupted or invalid. Rebuilding cache from the original source\n{e}")
+        else:
+            print(f"[Info] Color dataset not found for {side.name}. Rebuilding cache from the original source...")
+        ds = self.build_color_dataset(side=side)
+        ds.save(path)
+        return ds
+
+    def load_optimized_color_dataset(self, side: Side):
+        from .models import CameraDataset
+        path = self.image_path_config.get_optimized_color_dataset_path(side=side)
+        if path.exists():
+            try:
+                return CameraDataset.load(path)
+            except Exception:
+                print("[Error] Optimized color dataset cache is corrupted or invalid.")
+        return None
+
+    def save_optimized_color_dataset(self, dataset, side: Side):
+        path = self.image_path_config.get_optimized_color_dataset_path(side=side)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        dataset.save(path)
+
+    def build_color_dataset(self, side: Side):
+        """image_data_io.py:228-297.  One difference, for the PNG-free path: when the RGB directory holds
+        no PNG, the frames listed are the raw ``.yuv`` ones (directory and file names then name those)."""
+        from .models import CameraDataset
+        cfg = self.image_path_config
+        interpolator = PoseInterpolator(pose_csv_path=cfg.get_hmd_pose_csv_path())
+        cam = self.load_camera_characteristics(side=side)
+        paths, prefix, directory = cfg.get_rgb_image_paths(side=side), "RGB", cfg.get_rgb_dir(side=side)
+        if not paths:
+            paths, prefix, directory = cfg.get_yuv_image_paths(side=side), "YUV", cfg.get_yuv_dir(side=side)
+        names, timestamps, positions, rotations = [], [], [], []
+        for path in paths:
+            ts = self._parse_timestamp_stem(path.stem, path.name, prefix=prefix)
+            if ts is None:
+                continue
+            pose = interpolator.interpolate_pose(ts)
+            if pose is None:
+                print(f"[Warning] No pose found for timestamp {ts}. Skipping this image.")
+                continue
+            names.append(path.name)
+            timestamps.append(ts)
+            positions.append(pose[0])
+            rotations.append(pose[1])
+        if len(timestamps) == 0:
+            raise Exception("[Error] No valid timestamps found. Unable to build color dataset for side: {}.".format(
+                side.name))
+        hmd = Transforms(coordinate_system=CoordinateSystem.UNITY, positions=np.array(positions),
+                         rotations=np.array(rotations))
+        camera = hmd.apply_local_transform(local_position=cam.transl, local_rotation=cam.rot_quat)
+        # (np.full_like of the integer timestamps, as the reference: the intrinsics are truncated to integers)
+        return CameraDataset(
+            directory_relative_path=str(cfg.get_relative_path(directory)), image_file_names=np.array(names),
+            timestamps=np.array(timestamps), fx=np.full_like(timestamps, cam.fx), fy=np.full_like(timestamps, cam.fy),
+            cx=np.full_like(timestamps, cam.cx), cy=np.full_like(timestamps, cam.cy), transforms=camera,
+            widths=np.full_like(timestamps, cam.width), heights=np.full_like(timestamps, cam.height))
+
+
+class DataIO:
+    """The two sides of a capture directory: ``.depth`` (DepthDataIO) and ``.color`` (ImageDataIO)."""
+
+    def __init__(self, project_dir: Path):
+        self.project_dir = Path(project_dir).resolve()
+        self.depth = DepthDataIO(self.project_dir)
+        self.color = ImageDataIO(self.project_dir)

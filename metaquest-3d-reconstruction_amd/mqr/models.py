@@ -114,6 +114,13 @@ class Transforms:
         return Transforms(self.coordinate_system, delta.apply(self.positions) + delta_position,
                           (delta * Rotation.from_quat(self.rotations)).as_quat())
 
+    def apply_local_transform(self, local_position: np.ndarray, local_rotation: np.ndarray) -> "Transforms":
+        """Every pose composed with one child pose given in its own frame (transforms.py:223-239): the
+        camera's place on the headset.  local_rotation is (x, y, z, w)."""
+        parent = Rotation.from_quat(self.rotations)
+        return Transforms(self.coordinate_system, self.positions + parent.apply(local_position),
+                          (parent * Rotation.from_quat(local_rotation)).as_quat())
+
     def to_dict(self) -> dict:
         return {"coordinate_system": self.coordinate_system, "positions": self.positions,
                 "rotations": self.rotations}
@@ -254,3 +261,53 @@ class ConfidenceMap:
     @property
     def shape(self):
         return self.confidence_map.shape
+
+
+# ---- colour camera records (models/image_format_info.py, models/camera_characteristics.py,
+# config/yuv_to_rgb_config.py)
+@dataclass
+class ImagePlaneInfo:
+    buffer_size: int
+    row_stride: int
+    pixel_stride: int
+
+
+@dataclass
+class BaseTime:
+    mono_time_ns: int
+    unix_time_ns: int
+
+
+@dataclass
+class ImageFormatInfo:
+    width: int
+    height: int
+    format: str
+    planes: list
+    base_time: BaseTime
+
+
+@dataclass
+class CameraCharacteristics:
+    width: int
+    height: int
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    transl: np.ndarray    # head from camera
+    rot_quat: np.ndarray  # head from camera as quaternion (x, y, z, w)
+
+
+@dataclass
+class Yuv2RgbConfig:
+    blur_filter: bool
+    blur_threshold: float
+    exposure_filter: bool
+    exposure_threshold_low: float
+    exposure_threshold_high: float
+
+    @classmethod
+    def parse(cls, yuv_to_rgb_config_dict: dict) -> "Yuv2RgbConfig":
+        return cls(**{k: yuv_to_rgb_config_dict[k] for k in ("blur_filter", "blur_threshold", "exposure_filter",
+                                                             "exposure_threshold_low", "exposure_threshold_high")})

@@ -190,106 +190,26 @@ __global__ __launch_bounds__(256) void k_cm_vertices(const float* __restrict__ V
     counts[i] = cnt;
 }
 
-// ---- knn over the sampled vertices: Morton-sorted buckets of kBucket points under an implicit
-// complete binary tree of bucket boxes (heap order, leaves at P + b); exact search in float64.  The tree
-// build and the float32 box bound are bucket_tree.hpp's.
-#ifndef MQR_KNN_WAVE
-#define MQR_KNN_WAVE 1  // k_cm_knn_fill_wave (1) or the per-lane traversal k_cm_knn_fill (0): A/B builds
-#endif
-
+// ---- knn over the sampled vertices: bucket_tree.hpp's Morton-bucket tree (built by bucket_tree.hip), exact
+// search in float64.
+//
 // The knn (3) nearest sampled vertices of every unseen vertex (exact: float64 squared distances of the
 // float32 positions, ties by vertex index, the oracle's k-d tree rule), then the mean of their colours.
 // K = knn at compile time: the running best list lives in registers (static indices, an unrolled
-// insertion), and the traversal stack in LDS (stack-major: lane t's entry sp at stk[sp * 256 + t],
-// conflict-free), sized by the host to the tree's depth + 2 (a nearest-first DFS holds at most one pending
-// sibling per level plus the current pair): 20 entries for C5's 2^18 buckets instead of a fixed 32, so
-// more workgroups fit a CU's LDS.  Boxes are pruned and ordered in float32 on a proven lower bound
-// (box_d2_lb); candidates are compared exactly in float64.  The round-4 form kept a 64 x int64 stack and a
-// KMAX = 8 list with dynamic indices in scratch (64 ms for C5's 17.5 M unseen vertices), the first
-// round-5 form float64 box tests and a 32-entry stack (44.5 ms, profiles/r05_c5_kernel_stats.csv).
-template <int K>
-__global__ __launch_bounds__(256) void k_cm_knn_fill(const float* __restrict__ V, const int32_t* __restrict__ qids,
-                                                     int64_t nq, const float4* __restrict__ pts, int64_t n,
-                                                     int64_t P, const float4* __restrict__ lo,
-                                                     const float4* __restrict__ hi, const double* __restrict__ avg,
-                                                     float* __restrict__ out) {
-    extern __shared__ int32_t stk_lds[];
-    int32_t* stk = stk_lds + threadIdx.x;  // entry e of this lane at stk[256 e]
-    const int lane = threadIdx.x;
-    const int64_t t = (int64_t)blockIdx.x * blockDim.x + lane;
-    if (t >= nq) return;
-    const int32_t qv = qids[t];
-    const float qf[3] = {V[3 * (int64_t)qv], V[3 * (int64_t)qv + 1], V[3 * (int64_t)qv + 2]};
-    const double q[3] = {qf[0], qf[1], qf[2]};
-    double bd[K];
-    int32_t bi[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        bd[k] = __builtin_inf();  // an empty slot sorts after every real candidate
-        bi[k] = 0x7fffffff;
-    }
-    (void)lane;
-    int sp = 0;
-    stk[256 * sp++] = 1;
-    while (sp) {
-        const int32_t node = stk[256 * --sp];
-        if ((double)box_d2_lb(qf, lo[node], hi[node]) > bd[K - 1]) continue;  // (never while the list has room)
-        if (node >= P) {  // bucket
-            const int64_t b = node - P;
-            for (int64_t j = b * kBucket; j < min(n, (b + 1) * kBucket); ++j) {
-                const float4 pt = pts[j];
-                // float32 lower bound first (box_d2_lb's argument): most points of a visited bucket cannot
-                // enter the list, and those skip the float64 distance
-                const float fx = qf[0] - pt.x, fy = qf[1] - pt.y, fz = qf[2] - pt.z;
-                if ((double)((fx * fx + fy * fy + fz * fz) * (1.0f - 0x1p-18f)) > bd[K - 1]) continue;
-                const int32_t v = __float_as_int(pt.w);
-                const double dx = q[0] - (double)pt.x, dy = q[1] - (double)pt.y, dz = q[2] - (double)pt.z;
-                const double d2 = dx * dx + dy * dy + dz * dz;
-                auto before = [&](int k) { return d2 < bd[k] || (d2 == bd[k] && v < bi[k]); };  // new precedes k
-                if (!before(K - 1)) continue;
-                // insert at its rank among the K kept, sorted by (d2, index); the last one drops out.  From
-                // the end, with static indices: slot k takes slot k - 1's entry if the new one precedes it,
-                // else the new entry if it precedes slot k's, else keeps its own
-#pragma unroll
-                for (int k = K - 1; k >= 0; --k) {
-                    if (k > 0 && before(k - 1)) {
-                        bd[k] = bd[k - 1];
-                        bi[k] = bi[k - 1];
-                    } else if (before(k)) {
-                        bd[k] = d2;
-                        bi[k] = v;
-                    }
-                }
-            }
-        } else {  // nearer child popped first
-            const int32_t a = 2 * node, c = a + 1;
-            const float da = box_d2_lb(qf, lo[a], hi[a]), dc = box_d2_lb(qf, lo[c], hi[c]);
-            stk[256 * sp++] = da <= dc ? c : a;
-            stk[256 * sp++] = da <= dc ? a : c;
-        }
-    }
-    int nb = 0;
-    double c[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int k = 0; k < K; ++k)
-        if (bd[k] != __builtin_inf()) {
-            ++nb;
-#pragma unroll
-            for (int a = 0; a < 3; ++a) c[a] += avg[3 * (int64_t)bi[k] + a];
-        }
-    if (nb > 0)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) c[a] /= (double)nb;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) out[3 * (int64_t)qv + a] = (float)c[a];
-}
-
-// The same search with the traversal shared by a wave (MQR_KNN_WAVE): the wave's 64 queries -- neighbours in
-// vertex order, so close in space -- walk one stack of nodes together (node indices wave-uniform, read by
-// scalar loads), a node is skipped only when every lane's bound prunes it, and each lane keeps its own
-// exact best list.  A lane may so test nodes it would have pruned alone: that only offers it candidates
-// its own search would have rejected or met anyway, and the kept list is a total order on (d2, index), so
-// the result is the same.  Inactive lanes (past the query count) prune everything.
+// insertion).  Boxes are pruned and ordered in float32 on a proven lower bound (box_d2_lb); candidates are
+// prefiltered on the same bound and compared exactly in float64.
+// The traversal is shared by a wave: the wave's 64 queries -- neighbours in vertex order, so close in space --
+// walk one stack of nodes together (node indices wave-uniform, read by scalar loads; 64 entries per wave in
+// LDS, and a nearest-first DFS holds at most depth + 2), a node is skipped only when every lane's bound
+// prunes it, and each lane keeps its own exact best list.  A lane may so test nodes it would have pruned
+// alone: that only offers it candidates its own search would have rejected or met anyway, and the kept list
+// is a total order on (d2, index), so the result is the same.  Inactive lanes (past the query count) prune
+// everything.
+// History, C5's 17.5 M unseen vertices: one traversal per lane with a 64 x int64 stack and a KMAX = 8 list
+// with dynamic indices, both in scratch, 64 ms (round 4); float64 box tests and a 32-entry stack 44.5 ms,
+// then float32 bounds, the list in registers and a stack-major LDS stack of depth + 2 entries 23.8 ms (round
+// 5, profiles/r05_c5_kernel_stats.csv); this shared walk 12.7 ms (round 6, profiles/r06_ab_knn_wave.json: the
+// A/B that decided against the per-lane kernel).  meshcompare.hip's k_nn1 is the per-lane form still in use.
 template <int K>
 __global__ __launch_bounds__(256) void k_cm_knn_fill_wave(const float* __restrict__ V, const int32_t* __restrict__ qids,
                                                           int64_t nq, const float4* __restrict__ pts, int64_t n,
@@ -448,58 +368,37 @@ int cm_finish_colors(int device, hipStream_t s, const float* dV, int64_t nv, con
         if (!rc && nseen > 0)
             hipLaunchKernelGGL(k_cm_out_seen, dim3(gv), dim3(256), 0, s, avg, cnt, nv, dO);
         if (!rc && knn > 0 && nseen > 0 && nunseen > 0) {
-            const int64_t nb = (nseen + kBucket - 1) / kBucket;
-            int64_t P = 1;
-            while (P < nb) P <<= 1;
-            size_t tbs = 0;
-            if (hipcub::DeviceRadixSort::SortPairs(nullptr, tbs, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                   (const int32_t*)nullptr, (int32_t*)nullptr, (int)nseen, 0, 63, s) !=
-                hipSuccess)
-                fail("knn allocation failed");
-            blk_knn.reset(new CachedBlock(device, 24 + 16 * (size_t)nseen + 4 * (size_t)nseen + 64 * (size_t)P +
-                                                      16 * (size_t)nseen + tbs + 8 * 256));
+            // the tree's storage and its build scratch from a second block, sized by bucket_tree.hpp's rules
+            const size_t b_box = bucket_tree_node_bytes(nseen), b_scr = bucket_tree_scratch_bytes(nseen, false, s);
+            if (!b_scr) fail("knn allocation failed");
+            blk_knn.reset(new CachedBlock(device, 24 + 2 * b_box + 16 * (size_t)nseen + b_scr + 8 * 256));
             cur = blk_knn.get();
             uint32_t* bb = static_cast<uint32_t*>(alloc(6 * sizeof(uint32_t)));
-            uint64_t* keys = static_cast<uint64_t*>(alloc(sizeof(uint64_t) * 2 * nseen));
-            int32_t* sorted = static_cast<int32_t*>(alloc(sizeof(int32_t) * nseen));
-            float4* blo = static_cast<float4*>(alloc(sizeof(float4) * 2 * P));
-            float4* bhi = static_cast<float4*>(alloc(sizeof(float4) * 2 * P));
+            float4* blo = static_cast<float4*>(alloc(b_box));
+            float4* bhi = static_cast<float4*>(alloc(b_box));
             float4* pts = static_cast<float4*>(alloc(sizeof(float4) * nseen));
-            if (!rc && (!bb || !keys || !sorted || !blo || !bhi || !pts)) fail("knn allocation failed");
-            void* tmps = rc ? nullptr : alloc(tbs);
-            if (!rc && !tmps) fail("knn allocation failed");
+            void* scratch = rc ? nullptr : alloc(b_scr);
+            if (!rc && (!bb || !blo || !bhi || !pts || !scratch)) fail("knn allocation failed");
+            BucketTree t{};
+            if (!rc && bucket_tree_build(s, dV, ids, nseen, scratch, b_scr, blo, bhi, pts, bb, &t) != hipSuccess)
+                fail("knn tree build failed");
+            // the wave's stack holds 64 entries and a nearest-first DFS at most depth + 2 (depth <= 27 for
+            // fewer than 2^31 points in buckets of 16)
+            if (!rc && t.depth + 2 > 64) fail("the knn tree is too deep for the traversal stack");
             if (!rc) {
-                const uint32_t init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
-                const unsigned gs = (unsigned)((nseen + 255) / 256);
-                if (hipMemcpyAsync(bb, init, sizeof init, hipMemcpyHostToDevice, s) != hipSuccess) fail("copy");
-                hipLaunchKernelGGL(k_cm_bounds, dim3(std::min(gs, 4096u)), dim3(256), 0, s, dV, ids, nseen, bb);
-                hipLaunchKernelGGL(k_cm_morton, dim3(gs), dim3(256), 0, s, dV, ids, nseen, bb, keys);
-                if (hipcub::DeviceRadixSort::SortPairs(tmps, tbs, keys, keys + nseen, ids, sorted, (int)nseen, 0, 63, s) !=
-                    hipSuccess)
-                    fail("sort failed");
-                hipLaunchKernelGGL(k_cm_leaf_boxes, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, dV, sorted, nseen,
-                                   P, blo, bhi, pts);
-                for (int64_t first = P / 2; first >= 1; first /= 2)
-                    hipLaunchKernelGGL(k_cm_level, dim3((unsigned)((first + 255) / 256)), dim3(256), 0, s, first, first,
-                                       blo, bhi);
-                const dim3 gq((unsigned)((nunseen + 255) / 256));
-                int depth = 0;  // levels below the root of the P-leaf tree
-                while ((int64_t{1} << depth) < P) ++depth;
-                const bool wave = MQR_KNN_WAVE && depth + 2 <= 64;  // (the wave stack holds 64 entries)
-                const size_t lds = wave ? sizeof(int32_t) * 4 * 64 : sizeof(int32_t) * 256 * (size_t)(depth + 2);
                 auto fill = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, gq, dim3(256), lds, s, dV, ids + nv, nunseen, pts, nseen, P, blo, bhi,
-                                       avg, dO);
+                    hipLaunchKernelGGL(kern, dim3(nb(nunseen)), dim3(256), sizeof(int32_t) * 4 * 64, s, dV, ids + nv, nunseen,
+                                       t.pts, t.n, t.P, t.lo, t.hi, avg, dO);
                 };
                 switch (knn) {  // knn in [1, 8] (checked on entry)
-                    case 1: wave ? fill(k_cm_knn_fill_wave<1>) : fill(k_cm_knn_fill<1>); break;
-                    case 2: wave ? fill(k_cm_knn_fill_wave<2>) : fill(k_cm_knn_fill<2>); break;
-                    case 3: wave ? fill(k_cm_knn_fill_wave<3>) : fill(k_cm_knn_fill<3>); break;
-                    case 4: wave ? fill(k_cm_knn_fill_wave<4>) : fill(k_cm_knn_fill<4>); break;
-                    case 5: wave ? fill(k_cm_knn_fill_wave<5>) : fill(k_cm_knn_fill<5>); break;
-                    case 6: wave ? fill(k_cm_knn_fill_wave<6>) : fill(k_cm_knn_fill<6>); break;
-                    case 7: wave ? fill(k_cm_knn_fill_wave<7>) : fill(k_cm_knn_fill<7>); break;
-                    default: wave ? fill(k_cm_knn_fill_wave<8>) : fill(k_cm_knn_fill<8>); break;
+                    case 1: fill(k_cm_knn_fill_wave<1>); break;
+                    case 2: fill(k_cm_knn_fill_wave<2>); break;
+                    case 3: fill(k_cm_knn_fill_wave<3>); break;
+                    case 4: fill(k_cm_knn_fill_wave<4>); break;
+                    case 5: fill(k_cm_knn_fill_wave<5>); break;
+                    case 6: fill(k_cm_knn_fill_wave<6>); break;
+                    case 7: fill(k_cm_knn_fill_wave<7>); break;
+                    default: fill(k_cm_knn_fill_wave<8>); break;
                 }
             }
         }

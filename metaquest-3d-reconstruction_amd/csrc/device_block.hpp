@@ -35,6 +35,13 @@ struct CachedBlock {
     }
 };
 
+// The owner's side of that contract: declared after the block (so destroyed before it), it drains the stream
+// on every exit of the call before the block goes back to the cache.
+struct StreamDrain {
+    hipStream_t s;
+    ~StreamDrain() { (void)hipStreamSynchronize(s); }
+};
+
 // Grow-only device buffer, kept between calls by its owner (which also frees it, if ever).  A buffer is
 // regrown through hipFree, which waits for the device, so work a failed call left queued has finished with
 // it: regrowing under queued work is safe.

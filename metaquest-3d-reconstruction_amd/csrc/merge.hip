@@ -693,12 +693,8 @@ static int xchg_merge(Exchange& x, hipStream_t st, mqr_vbg* out) {
     return 0;
 }
 
-// Every exit of an exchange waits for its stream first: async copies read host memory of the
-// call (counts, the pinned plan summary) and a failing rank must not leave kernels in flight.
-struct StreamDrain {
-    hipStream_t s;
-    ~StreamDrain() { (void)hipStreamSynchronize(s); }
-};
+// Every exit of an exchange waits for its stream first (device_block.hpp's StreamDrain): async copies read
+// host memory of the call (counts, the pinned plan summary) and a failing rank must not leave kernels in flight.
 // A stream the call created: drained, then destroyed (one guard, so the order cannot invert).
 struct OwnedStream {
     hipStream_t s = nullptr;

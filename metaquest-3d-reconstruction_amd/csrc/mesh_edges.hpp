@@ -5,22 +5,16 @@
 // triangles in ascending order), then walks the runs: one run is one distinct edge, its length the number
 // of triangles on it.  A lock-free union-find hooked on the runs gives the connected components: the
 // filter unites the triangles of a run, the quality pass the two vertices of a key.  The kernels are
-// static: each including file gets its own copy.
+// static: each including file gets its own copy.  nb() and k_iota are device_prims.hpp's.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "device_prims.hpp"
+
 namespace mqr {
 namespace edges {
-
-// workgroups of `per` items that cover n (at least one)
-inline unsigned nb(int64_t n, int per = 256) { return (unsigned)((n > 0 ? n + per - 1 : per) / per); }
-
-static __global__ void k_iota(int32_t* a, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] = (int32_t)i;
-}
 
 // A loop edge (u == v, a degenerate triangle's) is a real key for the filter: Open3D's
 // ClusterConnectedTriangles counts it as adjacency, so two triangles that share one are one cluster.  The

@@ -3,11 +3,12 @@
 // Reference: analysis/computation/compare_mesh_to_ground_truth.py.  Its Open3D calls come down to three
 // primitives, each an entry point here (rules in DESIGN §2.6):
 //   mqr_nn_*            compute_point_cloud_distance / KDTreeFlann knn 1: the exact nearest target of every
-//                       query over bucket_tree.hpp's Morton-bucket tree, float64 on the widened float32
-//                       coordinates, d2 = (dx dx + dy dy) + dz dz, ties to the lowest target index;
+//                       query over bucket_tree.hpp's Morton-bucket tree (built by bucket_tree.hip), float64 on
+//                       the widened float32 coordinates, d2 = (dx dx + dy dy) + dz dz, ties to the lowest
+//                       target index;
 //   mqr_distance_stats  np.mean / np.std / np.min / np.max / np.median / (x < t).sum() of a distance array:
-//                       order-fixed float64 slab sums (pair_reduce.hpp), the median from a radix sort of the
-//                       bit patterns;
+//                       order-fixed float64 slab sums (device_prims.hpp), the median from a radix sort of
+//                       the bit patterns;
 //   mqr_mesh_measure    get_surface_area, get_axis_aligned_bounding_box, get_volume and the boundary edges of
 //                       count_holes, on one edge sort (mesh_edges.hpp, loop edges kept).
 // The file is built with -ffp-contract=off.  Scratch is one block of the device-block cache per call; a tree
@@ -17,25 +18,19 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstring>
 #include <string>
 
 #include "bucket_tree.hpp"
 #include "device_block.hpp"
+#include "device_prims.hpp"
 #include "mesh_edges.hpp"
 #include "mqr_common.hpp"
 #include "pair_reduce.hpp"
 
 struct mqr_nn {
     int device = 0;
-    int64_t n = 0;      // targets
-    int64_t P = 1;      // leaves of the complete tree (a power of two >= buckets)
-    int depth = 0;      // levels below the root
-    void* mem = nullptr;
-    float4* lo = nullptr;  // [2 P] node boxes, heap order
-    float4* hi = nullptr;
-    float4* pts = nullptr;  // [n] targets in Morton order: x, y, z, original index bits
-    uint32_t* bb = nullptr;  // the targets' bounds as ordered keys (the frame of the Morton keys)
+    void* mem = nullptr;     // one device allocation: the tree's boxes, points and bounds
+    mqr::BucketTree t{};     // over the targets; pts carry the original target index
 };
 
 struct mqr_edge_list {
@@ -57,22 +52,10 @@ constexpr int kSlab = kNS + 2;  // ... then one min and one max
 static StreamTable g_streams;
 
 // ------------------------------------------------------------------ checks
-// Reads the coordinates only; nothing gathers through them before the host has seen the flag.  A coordinate
-// passes when |a| <= limit (a NaN fails the comparison): FLT_MAX asks for finite values, and the search asks for
-// kCoordLimit, inside which the float32 bounds of bucket_tree.hpp cannot overflow: a difference is at most
-// 2e18, three squares of it 1.2e37 < FLT_MAX.  (An overflowed bound is +inf, which would prune a nearer point.)
+// device_prims.hpp's k_check_finite with FLT_MAX asks for finite values; the search asks for kCoordLimit,
+// inside which the float32 bounds of bucket_tree.hpp cannot overflow: a difference is at most 2e18, three
+// squares of it 1.2e37 < FLT_MAX.  (An overflowed bound is +inf, which would prune a nearer point.)
 constexpr float kCoordLimit = 1e18f;
-__global__ void k_check_finite(const float* __restrict__ a, int64_t n, float limit, int32_t* flag) {
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        bad |= !(fabsf(a[i]) <= limit);
-    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) *flag = 1;
-}
-
-__global__ void k_check_indices(const int32_t* __restrict__ tri, int64_t n, int64_t nv, int32_t* flag) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (tri[i] < 0 || (int64_t)tri[i] >= nv)) *flag = 1;
-}
 
 // ------------------------------------------------------------------ nearest neighbour
 // One query per lane, K = 1: the best (d2, index) pair in registers, the traversal stack in LDS (stack-major:
@@ -123,38 +106,6 @@ __global__ __launch_bounds__(256) void k_nn1(const float* __restrict__ Q, const 
     if (idx) idx[qi] = bi;
 }
 
-// ------------------------------------------------------------------ order-fixed reductions
-// The workgroup's kNS sums (pair_reduce.hpp), min and max into slab[0..kSlab).  Every lane calls it, once per kernel.
-__device__ inline void block_to_slab(const double (&acc)[kNS], double mn, double mx, double* __restrict__ slab) {
-    __shared__ double sh[pairsum::kWaves][kNS];
-    __shared__ double shm[pairsum::kWaves][2];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, off, 64));
-        mx = fmax(mx, __shfl_xor(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6][0] = mn, shm[threadIdx.x >> 6][1] = mx;
-    pairsum::block_sums_to_slab(acc, sh, slab);  // its barrier also covers shm
-    const int j = (int)threadIdx.x - kNS;
-    if (j == 0) slab[kNS] = fmin(fmin(shm[0][0], shm[1][0]), fmin(shm[2][0], shm[3][0]));
-    else if (j == 1) slab[kNS + 1] = fmax(fmax(shm[0][1], shm[1][1]), fmax(shm[2][1], shm[3][1]));
-}
-
-// One workgroup: lane l adds slabs l, l + kT, ... in that order, then the workgroup reduces as above.
-__global__ void __launch_bounds__(kT) k_reduce_slabs(const double* __restrict__ slabs, int64_t nblk,
-                                                     double* __restrict__ out) {
-    double acc[kNS] = {0.0, 0.0};
-    double mn = INFINITY, mx = -INFINITY;
-    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
-        const double* s = slabs + b * kSlab;
-#pragma unroll
-        for (int j = 0; j < kNS; ++j) acc[j] += s[j];
-        mn = fmin(mn, s[kNS]);
-        mx = fmax(mx, s[kNS + 1]);
-    }
-    block_to_slab(acc, mn, mx, out);
-}
-
 // ------------------------------------------------------------------ distance statistics
 struct StatsRes {
     double r0[kSlab];  // sum, count below the threshold, min, max
@@ -182,7 +133,7 @@ __global__ void __launch_bounds__(kT) k_stats(const double* __restrict__ x, int6
             acc[0] += (v - mean) * (v - mean);
         }
     }
-    block_to_slab(acc, mn, mx, slabs + (int64_t)blockIdx.x * kSlab);
+    block_sums_minmax_to_slab(acc, mn, mx, slabs + (int64_t)blockIdx.x * kSlab);
 }
 
 // numpy's median of the ascending array: the middle value, or the mean of the two middle ones
@@ -228,7 +179,7 @@ __global__ void __launch_bounds__(kT) k_tri_measure(const float* __restrict__ po
                      c2 = p1[0] * p2[1] - p1[1] * p2[0];
         acc[1] += ((p0[0] * c0 + p0[1] * c1) + p0[2] * c2) / 6.0;
     }
-    block_to_slab(acc, INFINITY, -INFINITY, slabs + (int64_t)blockIdx.x * kSlab);
+    block_sums_minmax_to_slab(acc, INFINITY, -INFINITY, slabs + (int64_t)blockIdx.x * kSlab);
 }
 
 // slot 3 t + e runs from corner e to corner e + 1 of triangle t: does it go from the lower index to the higher?
@@ -260,25 +211,6 @@ __global__ void k_boundary_pairs(const int32_t* __restrict__ slots, int64_t nb, 
     pairs[2 * i + 1] = max(a, b);
 }
 
-static int ceil_log2(int64_t n) {
-    int b = 0;
-    while (((int64_t)1 << b) < n) ++b;
-    return b;
-}
-
-static float host_from_ordered(uint32_t u) {
-    const uint32_t b = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    std::memcpy(&f, &b, sizeof f);
-    return f;
-}
-
-// every exit of a call drains its stream before the scratch block goes back to the cache
-struct Drain {
-    hipStream_t s;
-    ~Drain() { (void)hipStreamSynchronize(s); }
-};
-
 static int alloc_failed(const char* who, size_t want) {
     (void)hipGetLastError();
     set_error(std::string(who) + ": device allocation failed (needed " + std::to_string(want) + " bytes)");
@@ -304,26 +236,17 @@ int mqr_nn_create(int device, const float* targets, int64_t n, int loc, mqr_nn**
     hipStream_t s = g_streams.get(device);
     MQR_REQUIRE(s, "nn: no stream for the device");
 
-    const int64_t nbk = (n + kBucket - 1) / kBucket;
-    int64_t P = 1;
-    while (P < nbk) P <<= 1;
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                     (const int32_t*)nullptr, (int32_t*)nullptr, (int)n, 0, 63, s));
+    const size_t b_scr = bucket_tree_scratch_bytes(n, true, s);
+    MQR_REQUIRE(b_scr, "nn: the tree build's sort could not be sized");
     const bool host_in = loc == MQR_HOST;
     const size_t b_pos = host_in ? sizeof(float) * 3 * n : 0;
-    const size_t want = al256(b_pos) + 256 + 2 * al256(sizeof(uint64_t) * n) + 2 * al256(sizeof(int32_t) * n) +
-                        al256(tb + 16) + 256;
+    const size_t want = al256(b_pos) + 256 + b_scr + 256;
     CachedBlock blk(device, want);
     if (!blk.p) return alloc_failed("nn", want);
     float* d_pos = host_in ? (float*)blk.take(b_pos) : nullptr;
     int32_t* flag = (int32_t*)blk.take(sizeof(int32_t));
-    uint64_t* keys = (uint64_t*)blk.take(sizeof(uint64_t) * n);
-    uint64_t* keys_s = (uint64_t*)blk.take(sizeof(uint64_t) * n);
-    int32_t* ids = (int32_t*)blk.take(sizeof(int32_t) * n);
-    int32_t* sorted = (int32_t*)blk.take(sizeof(int32_t) * n);
-    void* tmp = blk.take(tb + 16);
-    if (!flag || !keys || !keys_s || !ids || !sorted || !tmp || (host_in && !d_pos)) return alloc_failed("nn", want);
+    void* scratch = blk.take(b_scr);
+    if (!flag || !scratch || (host_in && !d_pos)) return alloc_failed("nn", want);
 
     const float* pos = targets;
     if (host_in) {
@@ -332,7 +255,7 @@ int mqr_nn_create(int device, const float* targets, int64_t n, int loc, mqr_nn**
     } else if (order_after_caller(device, s)) {
         return 2;
     }
-    Drain drain{s};
+    StreamDrain drain{s};
 
     MQR_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(k_check_finite, dim3(std::min<unsigned>(nb(3 * n), 4096)), dim3(kT), 0, s, pos, 3 * n,
@@ -343,50 +266,23 @@ int mqr_nn_create(int device, const float* targets, int64_t n, int loc, mqr_nn**
     MQR_CHECK_HIP(hipStreamSynchronize(s));
     MQR_REQUIRE(!bad, "nn: a target coordinate is not finite or beyond 1e18 in magnitude");
 
+    // the tree keeps a plain allocation of its own: boxes, points, bounds
     mqr_nn* h = new mqr_nn();
     h->device = device;
-    h->n = n;
-    h->P = P;
-    h->depth = ceil_log2(P);
-    const size_t b_box = al256(sizeof(float4) * 2 * P), b_pts = al256(sizeof(float4) * n);
+    const size_t b_box = al256(bucket_tree_node_bytes(n)), b_pts = al256(sizeof(float4) * n);
     if (hipMalloc(&h->mem, 2 * b_box + b_pts + 256) != hipSuccess) {
         delete h;
         return alloc_failed("nn", 2 * b_box + b_pts + 256);
     }
     char* base = (char*)h->mem;
-    h->lo = (float4*)base;
-    h->hi = (float4*)(base + b_box);
-    h->pts = (float4*)(base + 2 * b_box);
-    h->bb = (uint32_t*)(base + 2 * b_box + b_pts);
-
-    int rc = 0;
-    auto step = [&](hipError_t e) {
-        if (e != hipSuccess && !rc) {
-            set_error(std::string("nn: tree build: ") + hipGetErrorString(e));
-            rc = 1;
-        }
-    };
-    const uint32_t init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
-    const unsigned gn = nb(n);
-    step(hipMemcpyAsync(h->bb, init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_iota, dim3(gn), dim3(kT), 0, s, ids, n);
-    hipLaunchKernelGGL(k_cm_bounds, dim3(std::min(gn, 4096u)), dim3(256), 0, s, pos, ids, n, h->bb);
-    hipLaunchKernelGGL(k_cm_morton, dim3(gn), dim3(256), 0, s, pos, ids, n, h->bb, keys);
-    step(hipGetLastError());
-    {
-        size_t t2 = tb;
-        step(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint64_t*)keys, keys_s, (const int32_t*)ids, sorted,
-                                                (int)n, 0, 63, s));
-    }
-    hipLaunchKernelGGL(k_cm_leaf_boxes, dim3(nb(P)), dim3(256), 0, s, pos, sorted, n, P, h->lo, h->hi, h->pts);
-    for (int64_t first = P / 2; first >= 1; first /= 2)
-        hipLaunchKernelGGL(k_cm_level, dim3(nb(first)), dim3(256), 0, s, first, first, h->lo, h->hi);
-    step(hipGetLastError());
-    step(hipStreamSynchronize(s));
-    if (rc) {
+    hipError_t e = bucket_tree_build(s, pos, nullptr, n, scratch, b_scr, (float4*)base, (float4*)(base + b_box),
+                                     (float4*)(base + 2 * b_box), (uint32_t*)(base + 2 * b_box + b_pts), &h->t);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        set_error(std::string("nn: tree build: ") + hipGetErrorString(e));
         (void)hipFree(h->mem);
         delete h;
-        return rc;
+        return 1;
     }
     *out = h;
     return 0;
@@ -411,7 +307,7 @@ int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* d
     MQR_CHECK_HIP(hipSetDevice(device));
     hipStream_t s = g_streams.get(device);
     MQR_REQUIRE(s, "nn: no stream for the device");
-    const size_t lds = sizeof(int32_t) * 256 * (size_t)(h->depth + 2);
+    const size_t lds = sizeof(int32_t) * 256 * (size_t)(h->t.depth + 2);
     MQR_REQUIRE(lds <= 64 * 1024, "nn: the tree is too deep for the traversal stack");
 
     size_t tb = 0;
@@ -443,7 +339,7 @@ int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* d
         Q = d_q;
     }
     if ((!host_in || !host_out) && order_after_caller(device, s)) return 2;
-    Drain drain{s};
+    StreamDrain drain{s};
 
     MQR_CHECK_HIP(hipMemsetAsync(flag, 0, sizeof(int32_t), s));
     hipLaunchKernelGGL(k_check_finite, dim3(std::min<unsigned>(nb(3 * nq), 4096)), dim3(kT), 0, s, Q, 3 * nq,
@@ -457,7 +353,7 @@ int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* d
     // queries in the Morton order of the tree's frame (a query outside the targets' box clamps to its faces)
     const unsigned gq = nb(nq);
     hipLaunchKernelGGL(k_iota, dim3(gq), dim3(kT), 0, s, ids, nq);
-    hipLaunchKernelGGL(k_cm_morton, dim3(gq), dim3(256), 0, s, Q, ids, nq, h->bb, keys);
+    bucket_tree_enqueue_keys(s, Q, ids, nq, h->t.bb, keys);
     MQR_CHECK_HIP(hipGetLastError());
     {
         size_t t2 = tb;
@@ -466,8 +362,8 @@ int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* d
     }
     double* o_d = host_out ? d_d : dist;
     int32_t* o_i = host_out ? d_i : idx;
-    hipLaunchKernelGGL(k_nn1, dim3(gq), dim3(256), lds, s, Q, (const int32_t*)order, nq, h->pts, h->n, h->P, h->lo,
-                       h->hi, o_d, o_i);
+    hipLaunchKernelGGL(k_nn1, dim3(gq), dim3(256), lds, s, Q, (const int32_t*)order, nq, h->t.pts, h->t.n, h->t.P,
+                       h->t.lo, h->t.hi, o_d, o_i);
     MQR_CHECK_HIP(hipGetLastError());
     if (host_out) {
         if (copy_to_host(device, dist, d_d, b_d, s)) return 1;
@@ -511,12 +407,12 @@ int mqr_distance_stats(int device, const double* dist, int64_t n, int loc, doubl
     } else if (order_after_caller(device, s)) {
         return 2;
     }
-    Drain drain{s};
+    StreamDrain drain{s};
 
     hipLaunchKernelGGL(k_stats<0>, dim3((unsigned)nblk), dim3(kT), 0, s, x, n, threshold, (const double*)nullptr, slabs);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk, res->r0);
+    hipLaunchKernelGGL(k_reduce_slabs<kNS>, dim3(1), dim3(kT), 0, s, slabs, nblk, res->r0);
     hipLaunchKernelGGL(k_stats<1>, dim3((unsigned)nblk), dim3(kT), 0, s, x, n, threshold, (const double*)res->r0, slabs);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk, res->r1);
+    hipLaunchKernelGGL(k_reduce_slabs<kNS>, dim3(1), dim3(kT), 0, s, slabs, nblk, res->r1);
     MQR_CHECK_HIP(hipGetLastError());
     {
         // non-negative doubles order as their bit patterns (the sign bit is clear: 63 key bits)
@@ -599,7 +495,7 @@ int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_
     } else if (order_after_caller(device, s)) {
         return 2;
     }
-    Drain drain{s};
+    StreamDrain drain{s};
 
     // ---- checks and bounds (no kernel gathers through an index before the flags are read)
     MQR_CHECK_HIP(hipMemsetAsync(ctrl, 0, sizeof(MeasureCtrl), s));
@@ -608,8 +504,7 @@ int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_
     hipLaunchKernelGGL(k_check_finite, dim3(std::min<unsigned>(nb(3 * nv), 4096)), dim3(kT), 0, s, pos, 3 * nv,
                        FLT_MAX, &ctrl->bad_coord);
     hipLaunchKernelGGL(k_iota, dim3(nb(nv)), dim3(kT), 0, s, vid, nv);
-    hipLaunchKernelGGL(k_cm_bounds, dim3(std::min<unsigned>(nb(nv), 4096)), dim3(256), 0, s, pos, (const int32_t*)vid,
-                       nv, ctrl->bb);
+    bucket_tree_enqueue_bounds(s, pos, vid, nv, ctrl->bb);
     MQR_CHECK_HIP(hipGetLastError());
     MeasureCtrl hc;
     MQR_CHECK_HIP(hipMemcpyAsync(&hc, ctrl, sizeof hc, hipMemcpyDeviceToHost, s));
@@ -619,8 +514,8 @@ int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_
 
     mqr_mesh_measure_result r{};
     for (int a = 0; a < 3; ++a) {
-        r.min_bound[a] = (double)host_from_ordered(hc.bb[a]);
-        r.max_bound[a] = (double)host_from_ordered(hc.bb[3 + a]);
+        r.min_bound[a] = (double)from_ordered(hc.bb[a]);
+        r.max_bound[a] = (double)from_ordered(hc.bb[3 + a]);
     }
     r.num_vertices = nv;
     r.num_triangles = nt;
@@ -631,7 +526,7 @@ int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_
 
     // ---- area and signed volume
     hipLaunchKernelGGL(k_tri_measure, dim3((unsigned)nblk_t), dim3(kT), 0, s, pos, tri, nt, slabs);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk_t, ctrl->sums);
+    hipLaunchKernelGGL(k_reduce_slabs<kNS>, dim3(1), dim3(kT), 0, s, slabs, nblk_t, ctrl->sums);
     // ---- the edge runs: boundary slots, closed and oriented
     hipLaunchKernelGGL(k_edge_keys<false>, dim3(nb(m)), dim3(kT), 0, s, tri, nt, (uint64_t)0, keys, slot);
     MQR_CHECK_HIP(hipGetLastError());

@@ -11,7 +11,7 @@
 // and one walk per vertex (vertex normals in Open3D's accumulation order, no float atomics) -> the sorted
 // edge list of mesh_edges.hpp (loop edges dropped) -> its union-find over vertices by run heads -> two
 // passes over run heads (sums, then squared deviations from the means).  Every mean and std is an
-// order-fixed float64 reduction (pair_reduce.hpp's slab per workgroup, the slabs summed by one workgroup
+// order-fixed float64 reduction (device_prims.hpp's slab per workgroup, the slabs summed by one workgroup
 // in a fixed order), so a repeated call is bit-identical.  Scratch is one block of the device-block cache.
 #include <hipcub/hipcub.hpp>
 
@@ -20,6 +20,7 @@
 #include <string>
 
 #include "device_block.hpp"
+#include "device_prims.hpp"
 #include "mesh_edges.hpp"
 #include "mqr_common.hpp"
 #include "pair_reduce.hpp"
@@ -38,10 +39,9 @@ constexpr double kEps = 1e-12;
 constexpr double kTheta = 1.0471975511965976;   // radians(60)
 constexpr double kRadToDeg = 57.29577951308232;  // 180 / pi, numpy's degrees() factor
 
-// control words (one small device region; mn is set to all ones, the rest to zero)
+// control words (one small device region; the box minimum is set to all ones, the rest to zero)
 struct Ctrl {
-    uint32_t mn[4];     // bounding box minimum as order-preserving keys
-    uint32_t mx[4];     // ... maximum
+    uint32_t bb[8];     // bounding box as order-preserving keys: min x y z, max x y z (two words unused)
     int32_t bad_index;  // a triangle index outside [0, nv)
     int32_t bad_coord;  // a non-finite coordinate
     int32_t roots;      // components of the vertex graph
@@ -56,55 +56,8 @@ struct Res {  // reduced slabs, read back by the host
     double density_std;
 };
 
-__device__ inline uint32_t order_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float order_val(uint32_t k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-
-// ------------------------------------------------------------------ order-fixed reductions
-// The workgroup's kNS sums (pair_reduce.hpp), min and max into slab[0..kSlab).  Every lane calls it, once per kernel.
-__device__ inline void block_to_slab(const double (&acc)[kNS], double mn, double mx, double* __restrict__ slab) {
-    __shared__ double sh[pairsum::kWaves][kNS];
-    __shared__ double shm[pairsum::kWaves][2];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        mn = fmin(mn, __shfl_xor(mn, off, 64));
-        mx = fmax(mx, __shfl_xor(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) shm[threadIdx.x >> 6][0] = mn, shm[threadIdx.x >> 6][1] = mx;
-    pairsum::block_sums_to_slab(acc, sh, slab);  // its barrier also covers shm
-    const int j = (int)threadIdx.x - kNS;
-    if (j == 0) slab[kNS] = fmin(fmin(shm[0][0], shm[1][0]), fmin(shm[2][0], shm[3][0]));
-    else if (j == 1) slab[kNS + 1] = fmax(fmax(shm[0][1], shm[1][1]), fmax(shm[2][1], shm[3][1]));
-}
-
-// One workgroup: lane l adds slabs l, l + kT, ... in that order, then the workgroup reduces as above.
-__global__ void __launch_bounds__(kT) k_reduce_slabs(const double* __restrict__ slabs, int64_t nblk,
-                                                     double* __restrict__ out) {
-    double acc[kNS];
-#pragma unroll
-    for (int j = 0; j < kNS; ++j) acc[j] = 0.0;
-    double mn = INFINITY, mx = -INFINITY;
-    for (int64_t b = threadIdx.x; b < nblk; b += kT) {
-        const double* s = slabs + b * kSlab;
-#pragma unroll
-        for (int j = 0; j < kNS; ++j) acc[j] += s[j];
-        mn = fmin(mn, s[kNS]);
-        mx = fmax(mx, s[kNS + 1]);
-    }
-    block_to_slab(acc, mn, mx, out);
-}
-
 // ------------------------------------------------------------------ checks, bounding box, density
-// Reads the index array only.
-__global__ void k_check_indices(const int32_t* __restrict__ tri, int64_t n, int64_t nv, Ctrl* c) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && (tri[i] < 0 || (int64_t)tri[i] >= nv)) c->bad_index = 1;
-}
-
+// The finite check and the box in one pass over the positions (the reduction is block_bounds_atomic's).
 __global__ void k_vertex_box(const float* __restrict__ pos, int64_t nv, Ctrl* c) {
     const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t step = (int64_t)gridDim.x * blockDim.x;
@@ -115,34 +68,13 @@ __global__ void k_vertex_box(const float* __restrict__ pos, int64_t nv, Ctrl* c)
         for (int a = 0; a < 3; ++a) {
             const float f = pos[3 * i + a];
             bad |= !isfinite(f);
-            const uint32_t k = order_key(f);
+            const uint32_t k = ordered_u32(f);
             mn[a] = min(mn[a], k);
             mx[a] = max(mx[a], k);
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            mn[a] = min(mn[a], (uint32_t)__shfl_xor((int)mn[a], off, 64));
-            mx[a] = max(mx[a], (uint32_t)__shfl_xor((int)mx[a], off, 64));
-        }
-    }
-    // one set of atomics per workgroup (a set per wave made the six words the kernel's whole cost: 1.1 ms
-    // for C5's 20.6 M vertices)
-    __shared__ uint32_t sh[kT / 64][6];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (__ballot(bad) != 0 && lane == 0) c->bad_coord = 1;
-    if (lane == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) sh[wave][a] = mn[a], sh[wave][3 + a] = mx[a];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int a = threadIdx.x;
-        atomicMin(&c->mn[a], min(min(sh[0][a], sh[1][a]), min(sh[2][a], sh[3][a])));
-        atomicMax(&c->mx[a], max(max(sh[0][3 + a], sh[1][3 + a]), max(sh[2][3 + a], sh[3][3 + a])));
-    }
+    if (__ballot(bad) != 0 && (threadIdx.x & 63) == 0) c->bad_coord = 1;
+    block_bounds_atomic(mn, mx, c->bb);
 }
 
 // The reference's voxel index per axis: clip(floor((p - min) / (extent / 10)), 0, 9), a true division.
@@ -152,8 +84,8 @@ __global__ void __launch_bounds__(kT) k_density_hist(const float* __restrict__ p
     double lo[3], vox[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        lo[a] = (double)order_val(c->mn[a]);
-        double ext = (double)order_val(c->mx[a]) - lo[a];
+        lo[a] = (double)from_ordered(c->bb[a]);
+        double ext = (double)from_ordered(c->bb[3 + a]) - lo[a];
         if (ext == 0.0) ext = 1e-6;
         vox[a] = ext / 10.0;
     }
@@ -190,7 +122,7 @@ __global__ void __launch_bounds__(kT) k_density_std(const Ctrl* __restrict__ c, 
     double vox[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        double ext = (double)order_val(c->mx[a]) - (double)order_val(c->mn[a]);
+        double ext = (double)from_ordered(c->bb[3 + a]) - (double)from_ordered(c->bb[a]);
         if (ext == 0.0) ext = 1e-6;
         vox[a] = ext / 10.0;
     }
@@ -282,7 +214,7 @@ __global__ void __launch_bounds__(kT) k_shape(const float* __restrict__ pos, con
         acc[1] += emax / emin;
         acc[2] += sk;
     }
-    block_to_slab(acc, INFINITY, -INFINITY, slabs + (int64_t)blockIdx.x * kSlab);
+    block_sums_minmax_to_slab(acc, INFINITY, -INFINITY, slabs + (int64_t)blockIdx.x * kSlab);
 }
 
 // ------------------------------------------------------------------ vertex normals
@@ -386,17 +318,11 @@ __global__ void __launch_bounds__(kT) k_edge_pass(const uint64_t* __restrict__ k
             }
         }
     }
-    block_to_slab(acc, mn, mx, slabs + (int64_t)blockIdx.x * kSlab);
+    block_sums_minmax_to_slab(acc, mn, mx, slabs + (int64_t)blockIdx.x * kSlab);
 }
 
 // ------------------------------------------------------------------ host
 static StreamTable g_streams;
-
-static int ceil_log2(int64_t n) {
-    int b = 0;
-    while (((int64_t)1 << b) < n) ++b;
-    return b;
-}
 
 }  // namespace mq
 }  // namespace mqr
@@ -474,16 +400,12 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
     } else if (order_after_caller(device, s)) {
         return 2;
     }
-    // From here on every exit drains `s` first: the block goes back to the cache at scope exit.
-    struct Drain {
-        hipStream_t s;
-        ~Drain() { (void)hipStreamSynchronize(s); }
-    } drain{s};
+    StreamDrain drain{s};
 
     // ---- checks (no kernel gathers through an index before the flags are read)
     MQR_CHECK_HIP(hipMemsetAsync(ctrl, 0, sizeof(Ctrl), s));
-    MQR_CHECK_HIP(hipMemsetAsync(ctrl->mn, 0xff, sizeof(ctrl->mn), s));
-    hipLaunchKernelGGL(k_check_indices, dim3(nb(m)), dim3(kT), 0, s, tri, m, nv, ctrl);
+    MQR_CHECK_HIP(hipMemsetAsync(ctrl->bb, 0xff, 3 * sizeof(uint32_t), s));
+    hipLaunchKernelGGL(k_check_indices, dim3(nb(m)), dim3(kT), 0, s, tri, m, nv, &ctrl->bad_index);
     hipLaunchKernelGGL(k_vertex_box, dim3(std::min<unsigned>(nb(nv), 4096)), dim3(kT), 0, s, pos, nv, ctrl);
     MQR_CHECK_HIP(hipGetLastError());
     int32_t flags[2] = {0, 0};
@@ -497,7 +419,7 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
     hipLaunchKernelGGL(k_density_std, dim3(1), dim3(kT), 0, s, ctrl, res);
     // ---- shape, triangle normals
     hipLaunchKernelGGL(k_shape, dim3((unsigned)nblk_t), dim3(kT), 0, s, pos, tri, nt, tn, slabs);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk_t, res->shape);
+    hipLaunchKernelGGL(k_reduce_slabs<kNS>, dim3(1), dim3(kT), 0, s, slabs, nblk_t, res->shape);
     MQR_CHECK_HIP(hipGetLastError());
     // ---- vertex normals: the corner sort borrows the edge sort's buffers
     {
@@ -527,10 +449,10 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
     // ---- smoothness and colour over run heads: sums, then squared deviations
     hipLaunchKernelGGL(k_edge_pass<0>, dim3((unsigned)nblk_e), dim3(kT), 0, s, keys_s, slot_s, m, none, vn, tn, col,
                        (const double*)nullptr, slabs);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk_e, res->e0);
+    hipLaunchKernelGGL(k_reduce_slabs<kNS>, dim3(1), dim3(kT), 0, s, slabs, nblk_e, res->e0);
     hipLaunchKernelGGL(k_edge_pass<1>, dim3((unsigned)nblk_e), dim3(kT), 0, s, keys_s, slot_s, m, none, vn, tn, col,
                        (const double*)res->e0, slabs);
-    hipLaunchKernelGGL(k_reduce_slabs, dim3(1), dim3(kT), 0, s, slabs, nblk_e, res->e1);
+    hipLaunchKernelGGL(k_reduce_slabs<kNS>, dim3(1), dim3(kT), 0, s, slabs, nblk_e, res->e1);
     MQR_CHECK_HIP(hipGetLastError());
 
     Res h;

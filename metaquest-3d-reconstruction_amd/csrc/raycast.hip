@@ -24,6 +24,7 @@
 
 #include "mqr_common.hpp"
 #include "device_block.hpp"
+#include "device_prims.hpp"
 
 struct mqr_scene {
     int device = 0;
@@ -53,56 +54,13 @@ constexpr uint32_t kInvalidId = 0xffffffffu;
 constexpr int kMaxDepth = 96;
 
 // ------------------------------------------------------------------ build
-__device__ inline uint32_t f2ord(float f) {  // order-preserving float -> uint32
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float ord2f(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
-
 struct BuildTri {
     float v[9];
 };
 
-// Gather every geometry's triangles into one array (prim id / geom id kept) and accumulate the
-// centroid bounds (ordered-int atomics).
-// Centroid bounds: a wave-wide min / max, then a workgroup-wide one (block_bounds_atomic).
-__device__ inline uint32_t wave_min_u32(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = min(x, (uint32_t)__shfl_xor((int)x, o, 64));
-    return x;
-}
-__device__ inline uint32_t wave_max_u32(uint32_t x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = max(x, (uint32_t)__shfl_xor((int)x, o, 64));
-    return x;
-}
-
-// Min / max of a workgroup's per-thread bounds (256 threads) into out[0..2] / out[3..5] by one atomic per
-// word and workgroup.
-__device__ inline void block_bounds_atomic(uint32_t (&lo)[3], uint32_t (&hi)[3], uint32_t* out) {
-    __shared__ uint32_t part[4][6];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const uint32_t wl = wave_min_u32(lo[a]), wh = wave_max_u32(hi[a]);
-        if (lane == 0) {
-            part[wave][a] = wl;
-            part[wave][3 + a] = wh;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        uint32_t r = part[0][c];
-        for (int w = 1; w < 4; ++w) r = c < 3 ? min(r, part[w][c]) : max(r, part[w][c]);
-        if (c < 3) atomicMin(&out[c], r);
-        else atomicMax(&out[c], r);
-    }
-}
-
-// Grid-stride over the triangles (a capped grid: one atomic per bound word and WORKGROUP -- per-wave
-// atomics on the same six words serialised this kernel to 44 ms for C5's 41 M triangles,
-// profiles/r05_c5_kernel_stats.csv).  256 threads per workgroup.
+// Gather every geometry's triangles into one array (prim id / geom id kept) and accumulate the centroid
+// bounds as ordered keys: grid-stride over the triangles on a capped grid, 256 threads per workgroup, one
+// atomic per bound word and workgroup (device_prims.hpp's block_bounds_atomic).
 constexpr unsigned kGatherGrid = 4096;
 __global__ __launch_bounds__(256) void k_gather_tris(const float* __restrict__ v, const int32_t* __restrict__ t,
                                                      int64_t nt, int64_t nv, int64_t base, uint32_t geom, BuildTri* tris,
@@ -127,7 +85,7 @@ __global__ __launch_bounds__(256) void k_gather_tris(const float* __restrict__ v
         prim[base + i] = (uint32_t)i;
         gid[base + i] = geom;
         for (int a = 0; a < 3; ++a) {
-            const uint32_t o = f2ord(c[a] * (1.0f / 3.0f));
+            const uint32_t o = ordered_u32(c[a] * (1.0f / 3.0f));
             lo[a] = min(lo[a], o);
             hi[a] = max(hi[a], o);
         }
@@ -135,23 +93,15 @@ __global__ __launch_bounds__(256) void k_gather_tris(const float* __restrict__ v
     block_bounds_atomic(lo, hi, cbounds);
 }
 
-__device__ inline uint64_t spread21(uint32_t x) {
-    uint64_t v = x & 0x1fffff;
-    v = (v | v << 32) & 0x1f00000000ffffull;
-    v = (v | v << 16) & 0x1f0000ff0000ffull;
-    v = (v | v << 8) & 0x100f00f00f00f00full;
-    v = (v | v << 4) & 0x10c30c30c30c30c3ull;
-    v = (v | v << 2) & 0x1249249249249249ull;
-    return v;
-}
-
+// (bucket_tree.hip's k_cm_morton quantises differently -- 2097151, x in the lowest bits: the BVH's shape and
+// the pinned tie cases depend on this form, so the two stay apart)
 __global__ void k_morton(const BuildTri* __restrict__ tris, int64_t n, const uint32_t* __restrict__ cb, uint64_t* keys,
                          uint32_t* idx) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint32_t q[3];
     for (int a = 0; a < 3; ++a) {
-        const float lo = ord2f(cb[a]), hi = ord2f(cb[3 + a]);
+        const float lo = from_ordered(cb[a]), hi = from_ordered(cb[3 + a]);
         const float c = (tris[i].v[a] + tris[i].v[3 + a] + tris[i].v[6 + a]) * (1.0f / 3.0f);
         const float ext = hi - lo;
         float s = ext > 0 ? (c - lo) / ext : 0.f;

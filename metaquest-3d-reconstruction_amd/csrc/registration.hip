@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "device_block.hpp"
+#include "device_prims.hpp"
 #include "mqr_common.hpp"
 #include "pair_reduce.hpp"
 
@@ -41,6 +42,7 @@ using pairsum::kThreads;
 using pairsum::kWaves;
 constexpr int kIcpSums = 17;   // count, sum q (3), sum t (3), sum q t^T (9), sum d^2
 constexpr double kCellLimit = 1048575.0;  // |cell index| < 2^20 per axis (pack_key)
+constexpr float kCoordLimit = 3.0e38f;    // a cloud's coordinates pass k_check_finite within it
 
 struct PairDesc {
     const float* src;       // source selection, view order
@@ -57,11 +59,6 @@ struct PairState {
 };
 
 // ------------------------------------------------------------------ kernels
-__global__ void k_check_finite(const float* __restrict__ p, int64_t n3, int* bad) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n3 && !(fabsf(p[i]) <= 3.0e38f)) atomicOr(bad, 1);
-}
-
 __global__ void k_every_k(const float* __restrict__ p, int64_t m, int64_t k, float* out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
@@ -335,8 +332,6 @@ __global__ __launch_bounds__(64) void k_finalize_info(const PairDesc* __restrict
 }
 
 // ------------------------------------------------------------------ host side
-inline unsigned nb(int64_t n) { return (unsigned)std::max<int64_t>((n + 255) / 256, 1); }
-
 struct Selection {  // points of one (cloud, kind, parameter)
     const float* pts = nullptr;
     int64_t n = 0;
@@ -651,7 +646,8 @@ int mqr_cloudset_create(int device, int n_clouds, const float* const* points, co
         }
         cs->pts.push_back(p);
         cs->counts.push_back(counts[i]);
-        hipLaunchKernelGGL(k_check_finite, dim3(nb(3 * counts[i])), dim3(256), 0, cs->s, p, 3 * counts[i], cs->d_flag);
+        hipLaunchKernelGGL(k_check_finite, dim3(std::min(nb(3 * counts[i]), 4096u)), dim3(256), 0, cs->s, p,
+                           3 * counts[i], kCoordLimit, cs->d_flag);
     }
     if (rc) return fail(rc);
     int flag = 0;

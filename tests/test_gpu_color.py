@@ -37,6 +37,19 @@ def scene():
     return mesh, imgs, K, T
 
 
+@pytest.fixture(scope="module")
+def partial_view(scene):
+    """3 of the 8 keyframes, which see only part of the room, and their colour-aligned depth cast from the mesh."""
+    from mqr.raycasting import RaycastingScene
+    mesh, imgs, K, T = scene
+    sel = [0, 3, 6]
+    imgs, K, T = imgs[sel], K[sel], T[sel]
+    rs = RaycastingScene()
+    rs.add_triangles(mesh.vertices, mesh.triangles)
+    t_hit = rs.cast_pinhole(K, T, 320, 240)["t_hit"].numpy()
+    return mesh, imgs, K, T, t_hit
+
+
 def test_color_matches_oracle(scene):
     from mqr.color import MARGIN, MAX_DEPTH, VISIBILITY_THRESHOLD, project_vertex_colors
     from mqr.raycasting import RaycastingScene
@@ -66,19 +79,13 @@ def test_color_thresholds_and_empty(scene):
     assert c.shape == (0, 3)
 
 
-def test_color_map_masks_and_fill_match_oracle(scene):
+def test_color_map_masks_and_fill_match_oracle(partial_view):
     """The complete colouring with 3 of the 8 keyframes: the depth-boundary masks drop samples at
     silhouettes (counts below the unmasked average's), and the vertices no keyframe samples take
     the mean of their 3 nearest sampled vertices -- all bit-identical to the oracle."""
-    from mqr.color import MARGIN, MAX_DEPTH, VISIBILITY_THRESHOLD, color_map, color_vertices
-    from mqr.raycasting import RaycastingScene
+    from mqr.color import color_map, color_vertices
     from mqr import synthetic
-    mesh, imgs, K, T = scene
-    sel = [0, 3, 6]
-    imgs, K, T = imgs[sel], K[sel], T[sel]
-    rs = RaycastingScene()
-    rs.add_triangles(mesh.vertices, mesh.triangles)
-    t_hit = rs.cast_pinhole(K, T, 320, 240)["t_hit"].numpy()
+    mesh, imgs, K, T, t_hit = partial_view
     gc, gn = color_map(mesh.vertices, imgs, t_hit, K, T)
     oc, on = oracle.color_map(mesh.vertices, imgs, t_hit, K, T)
     assert np.array_equal(gn, on)
@@ -90,3 +97,18 @@ def test_color_map_masks_and_fill_match_oracle(scene):
     assert (np.abs(gc[unseen]).sum(1) > 0).mean() > 0.99, "unseen vertices are filled from their neighbours"
     seen = ~unseen
     assert np.abs(gc[seen] - synthetic.texture(mesh.vertices[seen])).mean() < 0.05
+
+
+@pytest.mark.parametrize("knn", [1, 2, 8])
+def test_color_map_fill_matches_oracle_for_other_knn(partial_view, knn):
+    """The same partial view filled from 1, 2 and 8 neighbours: one search kernel serves every knn, and the
+    oracle check above exercises it at knn = 3 only.  Counts and colours bit-identical to the oracle."""
+    from mqr.color import color_map
+    mesh, imgs, K, T, t_hit = partial_view
+    gc, gn = color_map(mesh.vertices, imgs, t_hit, K, T, knn=knn)
+    oc, on = oracle.color_map(mesh.vertices, imgs, t_hit, K, T, knn=knn)
+    assert np.array_equal(gn, on)
+    assert np.array_equal(gc, oc)
+    unseen = gn == 0
+    assert 0.2 < unseen.mean() < 0.95
+    assert (np.abs(gc[unseen]).sum(1) > 0).mean() > 0.99, "unseen vertices are filled from their neighbours"

@@ -604,10 +604,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W8 ? 8 : 1,
                     ++n_pairs;
                     n_f32 += !dfr;
                 }
-#if MQR_CONF_BALLOT_DEFER  // (A/B library: the update behind a wave-uniform ballot)
-                if (__ballot(dfr))
-#endif
-                    defer |= (dmask_t)(dfr ? 1u : 0u) << (tt - clo);
+                defer |= (dmask_t)(dfr ? 1u : 0u) << (tt - clo);
                 nv += valid;
                 nc += cons;
             };

@@ -24,19 +24,12 @@
 //
 // Only extraction lives here.  The result handle (mqr_geom_*), the cached device block it is carved from
 // (geom_alloc) and the copies to the host are in devmem.hip.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
-#include <cstdlib>
 #include <string>
 
 #include "device_block.hpp"
 #include "mqr_common.hpp"
 #include "mqr_mc_tables.h"
-
-#ifndef MQR_AB
-#define MQR_AB 0  // 1: the extraction A/B modes (tools/_ab/libmqr_ab.so only, tools/ab_extract.py)
-#endif
 
 namespace mqr {
 
@@ -597,9 +590,10 @@ __device__ inline int mc_index(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
 }
 __device__ inline int mc_tri_count(int ci) { return (int)((mqr_tri_count_packed[ci >> 3] >> ((ci & 7) * 4)) & 0xFu); }
 
-// (nib: the per-cube counts as 4-bit fields, field x = the cube at origin x, for the emission pass)
+// Triangles of a voxel row's owned surface cubes; nib = the per-cube counts as 4-bit fields (field x =
+// the cube at origin x) for the emission pass.
 template <class M>
-__device__ inline int mc_row_tris(const uint32_t* rowN, uint32_t oc, int y, int z, uint64_t* nib = nullptr) {
+__device__ inline int mc_row_tris(const uint32_t* rowN, uint32_t oc, int y, int z, uint64_t& nib) {
     const uint32_t a = rowN[M::q(y, z)], b = rowN[M::q(y + 1, z)], c = rowN[M::q(y, z + 1)];
     const uint32_t d = rowN[M::q(y + 1, z + 1)];
     int n = 0;
@@ -611,7 +605,7 @@ __device__ inline int mc_row_tris(const uint32_t* rowN, uint32_t oc, int y, int 
         n += k;
         w |= (uint64_t)k << (4 * x);
     }
-    if (nib) *nib = w;
+    nib = w;
     return n;
 }
 
@@ -620,12 +614,12 @@ __device__ inline int mc_row_tris(const uint32_t* rowN, uint32_t oc, int y, int 
 // (owned crossing edges and owned surface cubes of the row) and the sign rows rowNt[b][q] of the
 // block's [-1, R]^3 tile (cube indices).  Emission of this block and of its -x / -y / -z
 // neighbours (triangles referencing vertices this block owns) read these instead of rebuilding them.
-// NIB: also the rows' per-cube triangle counts (rowsT[b][row], mc_row_tris) for the emission pass.
-template <int R, bool NIB = false>
+// Also the rows' per-cube triangle counts (rowsT[b][row], mc_row_tris) for the emission pass.
+template <int R>
 __global__ __launch_bounds__(kMcThreads) void k_mc_count(const int32_t* __restrict__ nb, const uint16_t* __restrict__ bits,
                                                          int64_t tri_blocks, int32_t* vcount, int32_t* tcount,
                                                          uint4* __restrict__ rows4, uint32_t* __restrict__ rowNt,
-                                                         uint64_t* __restrict__ rowsT = nullptr) {
+                                                         uint64_t* __restrict__ rowsT) {
     using M = Mc<R, 1>;
     __shared__ uint32_t rowV[M::S2], rowN[M::S2], cs[M::C2];
     __shared__ int32_t nbrow[27];
@@ -644,8 +638,8 @@ __global__ __launch_bounds__(kMcThreads) void k_mc_count(const int32_t* __restri
         e = mc_row<M>(rowN, cs, r % R, r / R);
         if (b >= tri_blocks) e.oc = 0;  // halo block of a shard: its vertices, none of its cubes
         nv = __popc(e.ex) + __popc(e.ey) + __popc(e.ez);
-        nt = mc_row_tris<M>(rowN, e.oc, r % R, r / R, NIB ? &tw : nullptr);
-        if constexpr (NIB) rowsT[b * M::R2 + r] = tw;
+        nt = mc_row_tris<M>(rowN, e.oc, r % R, r / R, tw);
+        rowsT[b * M::R2 + r] = tw;
     }
     int vtot, ttot;
     const int vb = block_exclusive_scan(nv, scratch, vtot);
@@ -816,11 +810,11 @@ __device__ __forceinline__ void mc_emit_vertex(int i, int lo, const uint4* rows,
 // Triangle i of a block (emission pass): its cube by binary search over the row triangle bases and a
 // walk over the row's owned cubes, its three vertex ids from the row records (this block's in LDS,
 // a +x / +y / +z neighbour's from rows4).
-// (tcs: the rows' per-cube triangle counts (NIB) -- the cube found by skipping 4-bit fields in
-// registers instead of a walk with a table lookup per cube)
-template <class M, bool NIB>
+// (tcs: the rows' per-cube triangle counts from the count pass -- the cube found by skipping 4-bit
+// fields in registers instead of a walk with a table lookup per cube)
+template <class M>
 __device__ __forceinline__ void mc_emit_tri(int i, int lo, const uint4* rows, const uint64_t* tcs, const uint32_t* rowN,
-                                            const uint32_t* triC, const uint64_t* triP, const int32_t* nbrow,
+                                            const uint64_t* triP, const int32_t* nbrow,
                                             const int32_t* __restrict__ voff, const uint4* __restrict__ rows4,
                                             int32_t vb0, int32_t tb0, int32_t* tri) {
     constexpr int R = M::C - 1;
@@ -828,31 +822,19 @@ __device__ __forceinline__ void mc_emit_tri(int i, int lo, const uint4* rows, co
     const int y = lo % R, z = lo / R;
     const uint32_t a = rowN[M::q(y, z)], bb = rowN[M::q(y + 1, z)], c = rowN[M::q(y, z + 1)];
     const uint32_t d = rowN[M::q(y + 1, z + 1)];
-    int k = i - (int)rw.y, x = 0, ci = 0;
-    if constexpr (NIB) {
-        uint64_t w = tcs[lo];  // non-zero fields = the owned surface cubes; k < their sum
-        for (;;) {
-            const int s = __builtin_ctzll(w) & ~3;
-            w >>= s;
-            x += s >> 2;
-            const int n = (int)(w & 0xFu);
-            if (k < n) break;
-            k -= n;
-            w >>= 4;
-            ++x;
-        }
-        ci = mc_index(a >> (x + 1), bb >> (x + 1), c >> (x + 1), d >> (x + 1));
-    } else {
-        uint32_t oc = rw.w >> 16;
-        while (oc) {
-            x = __builtin_ctz(oc);
-            ci = mc_index(a >> (x + 1), bb >> (x + 1), c >> (x + 1), d >> (x + 1));
-            const int n = (int)((triC[ci >> 3] >> ((ci & 7) * 4)) & 0xFu);
-            if (k < n) break;
-            k -= n;
-            oc &= oc - 1;
-        }
+    int k = i - (int)rw.y, x = 0;
+    uint64_t w = tcs[lo];  // non-zero fields = the owned surface cubes; k < their sum
+    for (;;) {
+        const int s = __builtin_ctzll(w) & ~3;
+        w >>= s;
+        x += s >> 2;
+        const int n = (int)(w & 0xFu);
+        if (k < n) break;
+        k -= n;
+        w >>= 4;
+        ++x;
     }
+    const int ci = mc_index(a >> (x + 1), bb >> (x + 1), c >> (x + 1), d >> (x + 1));
     const uint64_t te = triP[ci] >> (12 * k);
     const int64_t t = (int64_t)tb0 + i;
 #pragma unroll
@@ -885,16 +867,23 @@ __device__ __forceinline__ void mc_emit_tri(int i, int lo, const uint4* rows, co
 
 // Emission of a block with vertices or triangles, from the count pass's row records: vertices
 // (positions and normals from tsdf values gathered from the pool) and triangles at the offsets of
-// the scan, in (block, voxel, edge) / (block, cube, triangle) order.  role 0: both (one workgroup per
-// block, vertices then triangles); 1: vertices only; 2: triangles only (timing diagnostics).
-// (A merged vertex / triangle item loop, 512-thread blocks and a vertex and a triangle workgroup per
-// block were measured: no change or slower)
-// MAP: blocks with at most kRowMap vertices / triangles find each output's row in an LDS byte map
-// (filled by one pass over the rows) instead of by a binary search over the row bases.
+// the scan, in (block, voxel, edge) / (block, cube, triangle) order: one workgroup per block,
+// vertices then triangles.
+// Blocks with at most kRowMap vertices / triangles find each output's row in an LDS byte map (filled
+// by one pass over the rows); larger ones by a binary search over the row bases.
+// (Measured and removed, DESIGN.md §4.2.  Round 3: a merged vertex / triangle item loop, 512-thread
+// blocks and a vertex and a triangle workgroup per block -- no change or slower.  Round 4: the
+// emission over a compacted list of the blocks with output, by one workgroup per listed block or by a
+// grid of 8 workgroups per CU walking the list; the block's tsdf staged in LDS for its interior
+// vertices' taps; XCD bands of the pool in the count and emission passes; the triangles' neighbour
+// row records prefetched into LDS during the vertex loop -- all neutral or slower.  The three that
+// won are the code: the count pass's per-cube triangle counts (rowsT) instead of a table walk per
+// cube, the row maps, and the scan's totals written straight into pinned host memory instead of a
+// D2H copy enqueued between the scan and this pass, whose latency this pass waited behind.)
 constexpr int kRowMap = 2048;
 
-template <int R, int NT, bool NIB = false, bool MAP = false>
-__device__ __forceinline__ void mc_emit_block(int64_t b, int role, const int32_t* __restrict__ nb,
+template <int R, int NT>
+__device__ __forceinline__ void mc_emit_block(int64_t b, const int32_t* __restrict__ nb,
                                               const uint64_t* __restrict__ bkeys, const float2* __restrict__ pool,
                                               float voxel_size, const int32_t* __restrict__ vcount,
                                               const int32_t* __restrict__ tcount, const int32_t* __restrict__ voff,
@@ -908,10 +897,9 @@ __device__ __forceinline__ void mc_emit_block(int64_t b, int role, const int32_t
     __shared__ uint4 rows[M::R2];  // vbase, tbase, ex | ey << 16, ez | oc << 16
     __shared__ int32_t nbrow[27];
     __shared__ uint64_t triP[256];  // the triangle tables: lane-divergent lookups in a dependent loop
-    __shared__ uint32_t triC[32];
-    __shared__ uint64_t tcs[NIB ? M::R2 : 1];
-    __shared__ uint8_t vmap[MAP ? kRowMap : 1], tmap[MAP ? kRowMap : 1];
-    const int nvb = role == 2 ? 0 : vcount[b], ntb = role == 1 ? 0 : tcount[b];
+    __shared__ uint64_t tcs[M::R2];  // the rows' per-cube triangle counts (rowsT)
+    __shared__ uint8_t vmap[kRowMap], tmap[kRowMap];
+    const int nvb = vcount[b], ntb = tcount[b];
     if (nvb == 0 && ntb == 0) return;  // block-uniform: nothing to write
     const int32_t vb0 = voff[b], tb0 = toff[b];
     // outputs past the speculative capacity: the host re-runs this pass into exact buffers
@@ -919,19 +907,15 @@ __device__ __forceinline__ void mc_emit_block(int64_t b, int role, const int32_t
     // this speculative pass, which must not have written before the buffers' start)
     if (vb0 < 0 || tb0 < 0 || (int64_t)vb0 + vcount[b] > cap_v || (int64_t)tb0 + tcount[b] > cap_t) return;
     const int tid = threadIdx.x;
-    if (ntb) {
-        if (tid < 256) triP[tid] = mqr_tri_packed[tid];
-        if (tid < 32) triC[tid] = mqr_tri_count_packed[tid];
-    }
+    if (ntb && tid < 256) triP[tid] = mqr_tri_packed[tid];
     if (tid < 27) nbrow[tid] = nb[b * 27 + tid];
     for (int r = tid; r < M::R2; r += NT) rows[r] = rows4[b * M::R2 + r];
     if (ntb) {
         for (int q = tid; q < M::S2; q += NT) rowN[q] = rowNt[b * M::S2 + q];
-        if constexpr (NIB)
-            for (int r = tid; r < M::R2; r += NT) tcs[r] = rowsT[b * M::R2 + r];
+        for (int r = tid; r < M::R2; r += NT) tcs[r] = rowsT[b * M::R2 + r];
     }
     __syncthreads();
-    const bool vm = MAP && nvb <= kRowMap, tm = MAP && ntb <= kRowMap;  // block-uniform
+    const bool vm = nvb <= kRowMap, tm = ntb <= kRowMap;  // block-uniform
     if (vm || tm) {
         for (int r = tid; r < M::R2; r += NT) {
             const uint4 rw = rows[r];
@@ -958,31 +942,28 @@ __device__ __forceinline__ void mc_emit_block(int64_t b, int role, const int32_t
     }
     for (int i = tid; i < ntb; i += NT) {
         const int lo = tm ? (int)tmap[i] : row_search<M::R2, 1>(rows, i);
-        mc_emit_tri<M, NIB>(i, lo, rows, tcs, rowN, triC, triP, nbrow, voff, rows4, vb0, tb0, tri);
+        mc_emit_tri<M>(i, lo, rows, tcs, rowN, triP, nbrow, voff, rows4, vb0, tb0, tri);
     }
 }
 
-// diag (A/B library, MQR_EMIT_DIAG): 1 vertices only, 2 triangles only (timing of one half, wrong output)
-template <int R, bool NIB = false, bool MAP = false, int NT = kMcThreads>
+template <int R, int NT = kMcThreads>
 __global__ __launch_bounds__(NT) void k_mc_emit(const int32_t* __restrict__ nb, const uint64_t* __restrict__ bkeys,
                                                 const float2* __restrict__ pool, float voxel_size,
                                                 const int32_t* __restrict__ vcount, const int32_t* __restrict__ tcount,
                                                 const int32_t* __restrict__ voff, const int32_t* __restrict__ toff,
                                                 const uint4* __restrict__ rows4, const uint32_t* __restrict__ rowNt,
                                                 float* pos, float* nrm, int32_t* tri, int64_t cap_v, int64_t cap_t,
-                                                const uint64_t* __restrict__ rowsT, int diag = 0) {
-#if !MQR_AB
-    diag = 0;
-#endif
-    mc_emit_block<R, NT, NIB, MAP>(blockIdx.x, diag, nb, bkeys, pool, voxel_size, vcount, tcount, voff, toff, rows4,
-                                   rowNt, pos, nrm, tri, cap_v, cap_t, rowsT);
+                                                const uint64_t* __restrict__ rowsT) {
+    mc_emit_block<R, NT>(blockIdx.x, nb, bkeys, pool, voxel_size, vcount, tcount, voff, toff, rows4, rowNt, pos, nrm,
+                         tri, cap_v, cap_t, rowsT);
 }
-
 
 // (A decoupled look-back inside the count pass, one word per step or 64 per step, made the C2 count
 // pass 99 / 77 us against 31 + 5 here: each step is a cross-XCD round trip.)
 // Exclusive scans of the two per-block count arrays (vertices, triangles) in one workgroup of
-// kScanThreads; totals[0..1] = the sums.  (Two hipcub scans cost ~20 us of launches at these sizes.)
+// kScanThreads; totals[0..1] = the sums.  (Two hipcub scans cost ~20 us of launches at these sizes;
+// the byte-tile path, which once kept them, measured the same with either: 1.034 vs 1.036 ms per
+// extraction of the C2 scene at R = 12.)
 // Tiles of kScanTile counts: coalesced loads, all of a thread's in flight, staged in LDS; each
 // thread scans kScanPer consecutive counts, wave and workgroup scans of the thread sums; results
 // back through LDS to coalesced stores; a running carry between tiles.
@@ -1260,19 +1241,14 @@ __global__ __launch_bounds__(kThreads) void k_points(const int32_t* __restrict__
 
 
 // ---------------------------------------------------------------- host side
-// Carve the grow-only per-volume scratch: nb[27n], 4 count/offset arrays of n, faces[3R^2 n], scan temp.
+// Carve the grow-only per-volume scratch: nb[27n], 4 count/offset arrays of n, faces[3R^2 n], bits.
 struct ExScratch {
     int32_t *nb, *c0, *c1, *o0, *o1;
     uint32_t* faces;
     uint16_t* bits;  // k_mc_bits planes, 3 R^2 u16 per block (R = 8 / 16)
-    void* tmp;
-    size_t tmp_bytes;
 };
 
 static int ex_scratch(mqr_vbg* v, int64_t n, bool mesh, ExScratch& e) {
-    size_t tmp_bytes = 0;
-    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (const int32_t*)nullptr, (int32_t*)nullptr,
-                                                   (int)n, v->stream));
     const size_t sz_nb = al256(sizeof(int32_t) * 27 * n), sz_c = al256(sizeof(int32_t) * n);
     // mesh: the byte-tile path's face tables (3 R^2 u32 per block), or the bit-row path's row records
     // (R^2 uint4), sign rows ((R + 2)^2 u32) and per-cube triangle counts (R^2 u64) per block,
@@ -1282,8 +1258,7 @@ static int ex_scratch(mqr_vbg* v, int64_t n, bool mesh, ExScratch& e) {
                                      n)
                              : 0;
     const size_t sz_b = al256(sizeof(uint16_t) * 3 * v->R * v->R * n);
-    tmp_bytes = std::max<size_t>(tmp_bytes, 2 * sizeof(int64_t));
-    const size_t need = sz_nb + 4 * sz_c + sz_f + sz_b + al256(tmp_bytes);
+    const size_t need = sz_nb + 4 * sz_c + sz_f + sz_b;
     if (v->ex_scratch_bytes < need) {
         MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
         GrowBuf b{v->ex_scratch, v->ex_scratch_bytes};  // the volume holds the pair as two plain fields
@@ -1292,7 +1267,7 @@ static int ex_scratch(mqr_vbg* v, int64_t n, bool mesh, ExScratch& e) {
         v->ex_scratch_bytes = b.cap;
         MQR_CHECK_HIP(ex_scratch_alloc);
     }
-    // fine-grained (coherent) pinned memory: k_scan_counts writes the totals straight into it (ex_mode bit 2)
+    // fine-grained (coherent) pinned memory: k_scan_counts writes the totals straight into it
     if (!v->h_ex) MQR_CHECK_HIP(hipHostMalloc(&v->h_ex, 4 * sizeof(int64_t), hipHostMallocCoherent));
     char* p = static_cast<char*>(v->ex_scratch);
     e.nb = reinterpret_cast<int32_t*>(p);
@@ -1305,28 +1280,6 @@ static int ex_scratch(mqr_vbg* v, int64_t n, bool mesh, ExScratch& e) {
     e.faces = reinterpret_cast<uint32_t*>(p);
     p += sz_f;
     e.bits = reinterpret_cast<uint16_t*>(p);
-    p += sz_b;
-    e.tmp = p;
-    e.tmp_bytes = tmp_bytes;
-    return 0;
-}
-
-// Exclusive scans of up to two per-block count arrays; totals = last count + last offset (one sync).
-static int scan_totals(mqr_vbg* v, const ExScratch& e, int64_t n, int arrays, int64_t* tot0, int64_t* tot1) {
-    int32_t* h = reinterpret_cast<int32_t*>(v->h_ex);
-    size_t tb = e.tmp_bytes;
-    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(e.tmp, tb, e.c0, e.o0, (int)n, v->stream));
-    MQR_CHECK_HIP(hipMemcpyAsync(h + 0, e.c0 + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, v->stream));
-    MQR_CHECK_HIP(hipMemcpyAsync(h + 1, e.o0 + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, v->stream));
-    if (arrays > 1) {
-        tb = e.tmp_bytes;
-        MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(e.tmp, tb, e.c1, e.o1, (int)n, v->stream));
-        MQR_CHECK_HIP(hipMemcpyAsync(h + 2, e.c1 + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, v->stream));
-        MQR_CHECK_HIP(hipMemcpyAsync(h + 3, e.o1 + n - 1, sizeof(int32_t), hipMemcpyDeviceToHost, v->stream));
-    }
-    MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
-    *tot0 = (int64_t)h[0] + h[1];
-    if (arrays > 1) *tot1 = (int64_t)h[2] + h[3];
     return 0;
 }
 
@@ -1342,194 +1295,118 @@ static int build_nb(mqr_vbg* v, int32_t* nb) {
 // volume that is still being integrated.
 static int64_t spec_cap(int64_t hint) { return hint > 0 ? hint + hint / 4 + 4096 : 0; }
 
-// Extraction configuration: bit 0 = NIB (k_mc_count), bit 1 = MAP (k_mc_emit), bit 2 = the scan writes
-// the totals straight into pinned host memory (without: a D2H copy enqueued between the scan and the
-// emission pass, whose latency the emission waited behind); the A/B library takes it from
-// mqr_vbg_set_extract_mode (below; tools/ab_extract.py; a negative mode = the library default).  (Also measured in round 4
-// and removed, DESIGN.md §4.2: the emission over a compacted list of the blocks with output, by one
-// workgroup per listed block or by a grid of 8 workgroups per CU walking the list; the block's tsdf
-// staged in LDS for its interior vertices' taps; XCD bands of the pool in the count and emission
-// passes; the triangles' neighbour row records prefetched into LDS during the vertex loop -- all
-// neutral or slower.)
-[[maybe_unused]] constexpr int kExMode = 7;  // NIB + MAP + direct totals (tools/ab_extract.py)
-static int ex_mode(const mqr_vbg* v) {
-#if MQR_AB
-    return v->ex_mode < 0 ? kExMode : v->ex_mode;
-#else
-    (void)v;
-    return kExMode;
-#endif
+// Exclusive scans of the counts c0 (and c1) into o0 (and o1), the totals straight into the pinned h_ex.
+static void scan_counts(mqr_vbg* v, const ExScratch& e, int64_t n, bool two) {
+    hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(kScanThreads), 0, v->stream, e.c0, two ? e.c1 : nullptr, n, e.o0,
+                       two ? e.o1 : nullptr, v->h_ex);
 }
 
-template <int RT, bool NIB, bool MAP, class... A>
-static void launch_mc_emit_t(const mqr_vbg* v, int64_t n, A... args) {
-#if MQR_AB  // MQR_EMIT_DIAG=1: vertices only, 2: triangles only (timing diagnostics)
-    static const int diag = getenv("MQR_EMIT_DIAG") ? atoi(getenv("MQR_EMIT_DIAG")) : 0;
-#else
-    constexpr int diag = 0;
-#endif
-    hipLaunchKernelGGL((k_mc_emit<RT, NIB, MAP>), dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, args..., diag);
-}
-
-template <int RT, class... A>
-static void launch_mc_emit(const mqr_vbg* v, int64_t n, A... args) {
-    switch (ex_mode(v) & 3) {
-        case 1: launch_mc_emit_t<RT, true, false>(v, n, args...); break;
-        case 2: launch_mc_emit_t<RT, false, true>(v, n, args...); break;
-        case 3: launch_mc_emit_t<RT, true, true>(v, n, args...); break;
-        default: launch_mc_emit_t<RT, false, false>(v, n, args...); break;
+// What follows the scan's launch in every extraction.  With a previous extraction's counts in hint[]
+// (vertices and triangles, or points), emit into buffers of that size (+ margin) without waiting for
+// this one's totals; blocks past the capacity write nothing and the pass is re-run into exact buffers
+// if the totals exceed it.  Without (or hint == nullptr: an emission pass that does not bound its
+// writes), wait for the totals first.  emit(cap_v, cap_t) launches the emission pass into g's buffers.
+template <class Emit>
+static int emit_sized(mqr_vbg* v, mqr_geom* g, bool mesh, int64_t* hint, Emit emit) {
+    const int64_t cv = hint ? spec_cap(hint[0]) : 0, ct = hint && mesh ? spec_cap(hint[1]) : 0;
+    const bool spec = cv > 0 && (ct > 0 || !mesh);
+    if (spec && geom_alloc(g, cv, ct)) return 1;
+    MQR_CHECK_HIP(hipGetLastError());
+    if (spec) {
+        emit(cv, ct);
+        MQR_CHECK_HIP(hipGetLastError());
     }
+    MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
+    const int64_t nv = v->h_ex[0], nt = v->h_ex[1];  // (points: the scan of one array leaves nt = 0)
+    MQR_REQUIRE(nv < (int64_t)1 << 31 && nt < (int64_t)1 << 31,
+                mesh ? "mesh exceeds int32 vertex / triangle ids" : "point cloud exceeds int32 offsets");
+    if (hint) {
+        hint[0] = nv;
+        if (mesh) hint[1] = nt;
+    }
+    g->nv = nv;
+    g->nt = nt;
+    if (spec && nv <= cv && nt <= ct) return 0;
+    if (g->blk) {
+        geom_block_release(g->device, g->blk, g->blk_cap);
+        g->blk = nullptr;
+    }
+    if (geom_alloc(g, nv, nt)) return 1;
+    emit(nv, nt);
+    MQR_CHECK_HIP(hipGetLastError());
+    MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
+    return 0;
 }
 
 template <int RT>
 static int mesh_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g, int64_t tri_blocks) {
     const int64_t n = v->pool_count;
-    constexpr int RR = RT > 0 ? RT : 16;
-    uint4* rows4 = reinterpret_cast<uint4*>(e.faces);
-    uint32_t* rowNt = reinterpret_cast<uint32_t*>(rows4 + n * RR * RR);
-    uint64_t* rowsT = reinterpret_cast<uint64_t*>(rowNt + n * (RR + 2) * (RR + 2));  // 8-byte aligned: (R + 2)^2 even
-    int64_t nv = 0, nt = 0;
     if constexpr (RT > 0) {
-        int64_t* tot = reinterpret_cast<int64_t*>(e.tmp);
+        uint4* rows4 = reinterpret_cast<uint4*>(e.faces);
+        uint32_t* rowNt = reinterpret_cast<uint32_t*>(rows4 + n * RT * RT);
+        uint64_t* rowsT = reinterpret_cast<uint64_t*>(rowNt + n * (RT + 2) * (RT + 2));  // 8-byte aligned: (R + 2)^2 even
         hipLaunchKernelGGL(k_mc_bits<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, v->pool, thr, e.bits,
                            v->bkeys, v->tab, e.nb);
-        if (ex_mode(v) & 1)
-            hipLaunchKernelGGL((k_mc_count<RT, true>), dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, e.bits,
-                               tri_blocks, e.c0, e.c1, rows4, rowNt, rowsT);
-        else
-            hipLaunchKernelGGL((k_mc_count<RT, false>), dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, e.bits,
-                               tri_blocks, e.c0, e.c1, rows4, rowNt, rowsT);
-        const bool direct = ex_mode(v) & 4;
-        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(kScanThreads), 0, v->stream, e.c0, e.c1, n, e.o0, e.o1,
-                           direct ? v->h_ex : tot);
-        // With a previous extraction's counts, emit into buffers of that size (+ margin) without
-        // waiting for this one's totals; blocks past the capacity write nothing and the pass is re-run
-        // into exact buffers if the totals exceed it.  Without, wait for the totals first.
-        int64_t cv = spec_cap(v->ex_hint[0]), ct = spec_cap(v->ex_hint[1]);
-        const bool spec = cv > 0 && ct > 0;
-        if (spec && geom_alloc(g, cv, ct)) return 1;
-        MQR_CHECK_HIP(hipGetLastError());
-        if (!direct) MQR_CHECK_HIP(hipMemcpyAsync(v->h_ex, tot, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, v->stream));
-        bool emitted = false;
-        if (spec) {
-            launch_mc_emit<RT>(v, n, (const int32_t*)e.nb, (const uint64_t*)v->bkeys, (const float2*)v->pool,
-                               v->voxel_size, (const int32_t*)e.c0, (const int32_t*)e.c1, (const int32_t*)e.o0,
-                               (const int32_t*)e.o1, (const uint4*)rows4, (const uint32_t*)rowNt, g->pos, g->nrm,
-                               g->tri, cv, ct, (const uint64_t*)rowsT);
-            MQR_CHECK_HIP(hipGetLastError());
-            emitted = true;
-        }
-        MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
-        nv = v->h_ex[0];
-        nt = v->h_ex[1];
-        MQR_REQUIRE(nv < (int64_t)1 << 31 && nt < (int64_t)1 << 31, "mesh exceeds int32 vertex / triangle ids");
-        v->ex_hint[0] = nv;
-        v->ex_hint[1] = nt;
-        g->nv = nv;
-        g->nt = nt;
-        if (emitted && nv <= cv && nt <= ct) return 0;
-        if (g->blk) {
-            geom_block_release(g->device, g->blk, g->blk_cap);
-            g->blk = nullptr;
-        }
-        if (geom_alloc(g, nv, nt)) return 1;
-        launch_mc_emit<RT>(v, n, (const int32_t*)e.nb, (const uint64_t*)v->bkeys, (const float2*)v->pool, v->voxel_size,
-                           (const int32_t*)e.c0, (const int32_t*)e.c1, (const int32_t*)e.o0, (const int32_t*)e.o1,
-                           (const uint4*)rows4, (const uint32_t*)rowNt, g->pos, g->nrm, g->tri, nv, nt,
-                           (const uint64_t*)rowsT);
+        hipLaunchKernelGGL(k_mc_count<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, e.bits, tri_blocks,
+                           e.c0, e.c1, rows4, rowNt, rowsT);
+        scan_counts(v, e, n, true);
+        return emit_sized(v, g, true, v->ex_hint, [&](int64_t cap_v, int64_t cap_t) {
+            hipLaunchKernelGGL(k_mc_emit<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys, v->pool,
+                               v->voxel_size, e.c0, e.c1, e.o0, e.o1, rows4, rowNt, g->pos, g->nrm, g->tri, cap_v,
+                               cap_t, rowsT);
+        });
     } else {
         if (build_nb(v, e.nb)) return 1;
         hipLaunchKernelGGL(k_mesh_count<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->pool, v->R,
                            thr, e.c0, e.c1, e.faces);
-        MQR_CHECK_HIP(hipGetLastError());
-        if (scan_totals(v, e, n, 2, &nv, &nt)) return 1;
-        MQR_REQUIRE(nv < (int64_t)1 << 31 && nt < (int64_t)1 << 31, "mesh exceeds int32 vertex / triangle ids");
-        g->nv = nv;
-        g->nt = nt;
-        if (geom_alloc(g, nv, nt)) return 1;
-        hipLaunchKernelGGL(k_mesh_emit<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->bkeys,
-                           v->pool, v->R, v->voxel_size, thr, e.c0, e.c1, e.o0, e.o1, e.faces, g->pos, g->nrm, g->tri);
+        scan_counts(v, e, n, true);
+        return emit_sized(v, g, true, nullptr, [&](int64_t, int64_t) {
+            hipLaunchKernelGGL(k_mesh_emit<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->bkeys,
+                               v->pool, v->R, v->voxel_size, thr, e.c0, e.c1, e.o0, e.o1, e.faces, g->pos, g->nrm,
+                               g->tri);
+        });
     }
-    MQR_CHECK_HIP(hipGetLastError());
-    MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
-    return 0;
 }
 
 template <int RT>
 static int point_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g) {
     const int64_t n = v->pool_count;
-    int64_t np = 0;
     if constexpr (RT > 0) {
-        uint4* rows4 = reinterpret_cast<uint4*>(e.faces);
-        int64_t* tot = reinterpret_cast<int64_t*>(e.tmp);
+        uint4* rows4 = reinterpret_cast<uint4*>(e.faces);  // the row records use the mesh path's slot
         hipLaunchKernelGGL(k_mc_bits<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, v->pool, thr, e.bits,
                            v->bkeys, v->tab, e.nb);
         hipLaunchKernelGGL(k_pt_count<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, e.bits, v->pool,
                            e.c0, rows4);
-        const bool direct = ex_mode(v) & 4;
-        hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(kScanThreads), 0, v->stream, e.c0, (const int32_t*)nullptr, n,
-                           e.o0, (int32_t*)nullptr, direct ? v->h_ex : tot);
-        MQR_CHECK_HIP(hipGetLastError());
-        if (!direct) MQR_CHECK_HIP(hipMemcpyAsync(v->h_ex, tot, sizeof(int64_t), hipMemcpyDeviceToHost, v->stream));
-        const int64_t cp = spec_cap(v->ex_hint[2]);  // speculative capacity, as in mesh_passes
-        if (cp > 0) {
-            if (geom_alloc(g, cp, 0)) return 1;
+        scan_counts(v, e, n, false);
+        return emit_sized(v, g, false, v->ex_hint + 2, [&](int64_t cap, int64_t) {
             hipLaunchKernelGGL(k_pt_emit<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys,
-                               v->pool, v->voxel_size, e.c0, e.o0, reinterpret_cast<const uint4*>(e.faces), g->pos,
-                               g->nrm, cp);
-            MQR_CHECK_HIP(hipGetLastError());
-        }
-        MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
-        np = v->h_ex[0];
-        MQR_REQUIRE(np < (int64_t)1 << 31, "point cloud exceeds int32 offsets");
-        v->ex_hint[2] = np;
-        g->nv = np;
-        if (cp > 0 && np <= cp) return 0;
-        if (g->blk) {
-            geom_block_release(g->device, g->blk, g->blk_cap);
-            g->blk = nullptr;
-        }
-        if (geom_alloc(g, np, 0)) return 1;
-        hipLaunchKernelGGL(k_pt_emit<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys, v->pool,
-                           v->voxel_size, e.c0, e.o0, reinterpret_cast<const uint4*>(e.faces), g->pos, g->nrm, np);
+                               v->pool, v->voxel_size, e.c0, e.o0, rows4, g->pos, g->nrm, cap);
+        });
     } else {
         if (build_nb(v, e.nb)) return 1;
         hipLaunchKernelGGL(k_points<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->bkeys, v->pool,
                            v->R, v->voxel_size, thr, e.c0, (const int32_t*)nullptr, (float*)nullptr, (float*)nullptr);
-        MQR_CHECK_HIP(hipGetLastError());
-        if (scan_totals(v, e, n, 1, &np, nullptr)) return 1;
-        g->nv = np;
-        if (geom_alloc(g, np, 0)) return 1;
-        hipLaunchKernelGGL(k_points<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->bkeys, v->pool,
-                           v->R, v->voxel_size, thr, e.c0, e.o0, g->pos, g->nrm);
+        scan_counts(v, e, n, false);
+        return emit_sized(v, g, false, nullptr, [&](int64_t, int64_t) {
+            hipLaunchKernelGGL(k_points<RT>, dim3((unsigned)n), dim3(kThreads), 0, v->stream, e.nb, n, v->bkeys,
+                               v->pool, v->R, v->voxel_size, thr, e.c0, e.o0, g->pos, g->nrm);
+        });
     }
-    MQR_CHECK_HIP(hipGetLastError());
-    MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
-    return 0;
 }
 
-}  // namespace mqr
-
-using namespace mqr;
-
-extern "C" {
-
-int mqr_extract_mesh(mqr_vbg* v, float thr, mqr_geom** out) { return mqr_extract_mesh_owned(v, thr, -1, out); }
-
-#if MQR_AB
-// A/B library only: the extraction configuration (kExMode bits) for tools/ab_extract.py.
-int mqr_vbg_set_extract_mode(mqr_vbg* v, int mode) {
-    MQR_REQUIRE(v && mode < 8, "bad extraction mode");
-    v->ex_mode = mode;
-    return 0;
+template <int RT>
+static int passes(mqr_vbg* v, float thr, bool mesh, const ExScratch& e, mqr_geom* g, int64_t tri_blocks) {
+    return mesh ? mesh_passes<RT>(v, thr, e, g, tri_blocks) : point_passes<RT>(v, thr, e, g);
 }
-#endif
 
-int mqr_extract_mesh_owned(mqr_vbg* v, float thr, int64_t n_owned, mqr_geom** out) {
+// The body of both entry points: checks, ordering, the result handle, scratch, the passes for the
+// volume's R; a failed call frees what it allocated and keeps its message.
+static int extract(mqr_vbg* v, float thr, bool mesh, int64_t n_owned, mqr_geom** out) {
+    const std::string name = mesh ? "extract_triangle_mesh" : "extract_point_cloud";
     MQR_REQUIRE(v && out, "null argument");
-    MQR_REQUIRE(v->R <= kMaxR, "extract_triangle_mesh supports block_resolution <= 16");
+    MQR_REQUIRE(v->R <= kMaxR, name + " supports block_resolution <= 16");
     // (at R = 1 the tile [-1, R + 1] would reach two blocks away)
-    MQR_REQUIRE(v->R >= 2, "extract_triangle_mesh needs block_resolution >= 2, got " + std::to_string(v->R));
+    MQR_REQUIRE(v->R >= 2, name + " needs block_resolution >= 2, got " + std::to_string(v->R));
     MQR_REQUIRE(n_owned < 0 || v->R == 16 || v->R == 8, "owned-block extraction supports block_resolution 8 / 16");
     const int64_t tri_blocks = n_owned < 0 ? INT64_MAX : n_owned;
     MQR_CHECK_HIP(hipSetDevice(v->device));
@@ -1541,10 +1418,10 @@ int mqr_extract_mesh_owned(mqr_vbg* v, float thr, int64_t n_owned, mqr_geom** ou
     int rc = 0;
     if (n > 0) {
         ExScratch e{};
-        rc = ex_scratch(v, n, true, e);
-        if (!rc) rc = v->R == 16 ? mesh_passes<16>(v, thr, e, g, tri_blocks)
-                      : v->R == 8 ? mesh_passes<8>(v, thr, e, g, tri_blocks)
-                                  : mesh_passes<0>(v, thr, e, g, tri_blocks);
+        rc = ex_scratch(v, n, true, e);  // (points too: their row records use the mesh path's slot)
+        if (!rc) rc = v->R == 16 ? passes<16>(v, thr, mesh, e, g, tri_blocks)
+                      : v->R == 8 ? passes<8>(v, thr, mesh, e, g, tri_blocks)
+                                  : passes<0>(v, thr, mesh, e, g, tri_blocks);
     }
     if (rc) {  // release whatever the failed passes allocated; the caller gets no handle
         const std::string msg = get_error();
@@ -1556,31 +1433,18 @@ int mqr_extract_mesh_owned(mqr_vbg* v, float thr, int64_t n_owned, mqr_geom** ou
     return 0;
 }
 
-int mqr_extract_points(mqr_vbg* v, float thr, mqr_geom** out) {
-    MQR_REQUIRE(v && out, "null argument");
-    MQR_REQUIRE(v->R <= kMaxR, "extract_point_cloud supports block_resolution <= 16");
-    MQR_REQUIRE(v->R >= 2, "extract_point_cloud needs block_resolution >= 2, got " + std::to_string(v->R));
-    MQR_CHECK_HIP(hipSetDevice(v->device));
-    if (order_after_integrate(v)) return 1;
-    const int64_t n = v->pool_count;
-    mqr_geom* g = new mqr_geom();
-    g->device = v->device;
-    *out = nullptr;
-    int rc = 0;
-    if (n > 0) {
-        ExScratch e{};
-        rc = ex_scratch(v, n, true, e);  // the row records use the mesh path's slot
-        if (!rc) rc = v->R == 16 ? point_passes<16>(v, thr, e, g) : v->R == 8 ? point_passes<8>(v, thr, e, g)
-                                                                           : point_passes<0>(v, thr, e, g);
-    }
-    if (rc) {
-        const std::string msg = get_error();
-        mqr_geom_free(g);
-        set_error(msg);
-        return rc;
-    }
-    *out = g;
-    return 0;
+}  // namespace mqr
+
+using namespace mqr;
+
+extern "C" {
+
+int mqr_extract_mesh(mqr_vbg* v, float thr, mqr_geom** out) { return extract(v, thr, true, -1, out); }
+
+int mqr_extract_mesh_owned(mqr_vbg* v, float thr, int64_t n_owned, mqr_geom** out) {
+    return extract(v, thr, true, n_owned, out);
 }
+
+int mqr_extract_points(mqr_vbg* v, float thr, mqr_geom** out) { return extract(v, thr, false, -1, out); }
 
 }  // extern "C"

@@ -1395,7 +1395,6 @@ int mqr_vbg_set_variant(mqr_vbg* v, int variant) {
     v->flip_reset = (variant & 0x2000000) == 0;   // bit 25: reset waits for an in-flight integrate (no set swap, A/B)
     v->rtab = (variant & 0x4000000) == 0;         // bit 26: k_integrate_win instead of the LDS-table kernel (A/B)
     v->div1 = (variant & 0x8000000) == 0;         // bit 27: the LDS-table kernel keeps two quotient corrections (A/B)
-    // (the extraction configuration is set by mqr_vbg_set_extract_mode alone, A/B library only)
     return 0;
 }
 

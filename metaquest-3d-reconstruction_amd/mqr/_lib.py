@@ -261,7 +261,7 @@ def load(path: str = LIB_PATH):
     partial = os.path.abspath(path) != os.path.abspath(os.path.join(_HERE, "libmqr_hip.so"))
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(L, name, None)
-        if fn is None and partial:  # the A/B library (tools/_ab) carries the volume entry points only
+        if fn is None and partial:  # a variant library (tools/build_*_variants.sh) carries some entry points only
             continue
         fn = getattr(L, name)
         fn.restype = res

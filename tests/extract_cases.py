@@ -48,7 +48,6 @@ SPARSE = (8, SCAN_TILE + 300, 8)      # (R, blocks, seed)
 OWNED = (8, 4, 9)                     # (R, G, seed)
 SPHERES = {8: 4, 12: 4}               # R -> G; radius = SPHERE_RADIUS * R voxels
 SPHERE_RADIUS = 1.4125                # x R: 11.3 voxels at R = 8, through the block corners (+-R, +-R, 0)
-AB_VOLUMES = (("dense", 16, 4, 10), ("dense", 8, 6, 10), ("mixed", 16) + MIXED[16][:2])
 
 
 class Volume(NamedTuple):
@@ -267,52 +266,3 @@ def sphere_errors(pos, nrm, radius, centre=(0.3, -0.2, 0.1), voxel_size=VOXEL_SI
     d = np.linalg.norm(p, axis=1)
     return float(np.abs(d - radius).max()), float(((np.asarray(nrm, np.float64) * p).sum(1) / d).min())
 
-
-# ---- A/B child -----------------------------------------------------------------------------------
-
-def ab_volume(spec):
-    kind, R, G, seed = spec
-    if kind == "dense":
-        return dense_signs(R, G, seed)
-    return dense_signs(R, G, seed, weights="mixed", drop=MIXED[R][2])
-
-
-def _ab_child():
-    """Run with MQR_HIP_LIB naming the A/B library: extracts each of AB_VOLUMES under the extraction
-    modes 0..3 and the default (-1) and prints one JSON line {volume: {mode: sha1 of positions,
-    normals, triangles}}."""
-    import ctypes
-    import hashlib
-    import json
-    sys.path.insert(0, os.path.join(ROOT, "metaquest-3d-reconstruction_amd"))
-    from mqr import _lib
-    from mqr.vbg import VoxelBlockGrid
-    _lib.load()
-    out = {}
-    for spec in AB_VOLUMES:
-        vol = ab_volume(spec)
-        vbg = VoxelBlockGrid(voxel_size=VOXEL_SIZE, block_resolution=vol.R, block_count=len(vol.keys) + 16, device=0)
-        vbg.import_blocks(*vol[:3])
-        res = {}
-        for mode in (0, 1, 2, 3, -1):
-            _lib.call("mqr_vbg_set_extract_mode", vbg.handle, mode)
-            g = ctypes.c_void_p()
-            _lib.call("mqr_extract_mesh", vbg.handle, float(THRESHOLD), ctypes.byref(g))
-            nv, nt = ctypes.c_int64(), ctypes.c_int64()
-            _lib.call("mqr_geom_counts", g, ctypes.byref(nv), ctypes.byref(nt))
-            p = np.empty((nv.value, 3), np.float32)
-            n = np.empty((nv.value, 3), np.float32)
-            t = np.empty((nt.value, 3), np.int32)
-            _lib.call("mqr_geom_copy", g, p.ctypes.data_as(ctypes.c_void_p), n.ctypes.data_as(ctypes.c_void_p),
-                      t.ctypes.data_as(ctypes.c_void_p), 0)
-            _lib.call("mqr_geom_free", g)
-            h = hashlib.sha1()
-            for a in (p, n, t):
-                h.update(a.tobytes())
-            res[str(mode)] = f"{nv.value}:{nt.value}:{h.hexdigest()}"
-        out["%s_R%d_G%d_s%d" % spec] = res
-    print(json.dumps(out))
-
-
-if __name__ == "__main__":
-    _ab_child()

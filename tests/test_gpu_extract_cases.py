@@ -12,10 +12,6 @@ vertices and points, (block, cube, triangle) for triangles), which mesh_passes a
 extraction's triangle prefix rely on.
 """
 import ctypes
-import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -25,8 +21,6 @@ import oracle
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-AB_LIB = os.path.join(ROOT, "tools", "_ab", "libmqr_ab.so")
 THR = ec.THRESHOLD
 
 
@@ -242,23 +236,6 @@ def test_sphere(R):
     # voxel at r = 11.3 (less at R = 12): 0.05 voxel leaves room, one voxel would hide a wrong tap
     err, dot = ec.sphere_errors(gv, gn, radius)
     assert err < 0.05 and dot > 0.99, (err, dot)
-
-
-def test_ab_extraction_modes_agree_on_constructed_volumes():
-    """The A/B library's extraction modes (per-cube counts from the count pass, LDS row maps; 0..3 and
-    the default) on a dense R = 16, a dense R = 8 and the mixed R = 16 volume, in one child process:
-    one hash of (positions, normals, triangles) per mode and volume, all equal per volume."""
-    assert os.path.exists(AB_LIB), f"{AB_LIB} missing: run __graft_entry__.build()"
-    env = dict(os.environ, MQR_HIP_LIB=AB_LIB)
-    r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "tests", "extract_cases.py")], cwd=ROOT, env=env,
-                       capture_output=True, text=True, timeout=240)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    res = json.loads(r.stdout.strip().splitlines()[-1])
-    assert len(res) == len(ec.AB_VOLUMES)
-    for name, modes in res.items():
-        assert set(modes) == {"0", "1", "2", "3", "-1"}, name
-        assert len(set(modes.values())) == 1, (name, modes)
-        assert int(modes["-1"].split(":")[1]) > 1000, (name, modes)
 
 
 @pytest.mark.parametrize("kind", ["mesh", "points"])

@@ -21,7 +21,7 @@
 #   pmcint      SQ / TA / TCP counters of the default integrate kernel (tools/pmc_ab.sh) -> profiles_new/
 #   pmcconf     counter passes of the confidence kernel (tools/pmc_conf.sh) -> profiles_new/${TAG}_pmc_confidence.json
 #   abint:V     tools/ab_integrate.py over integrate variants V (comma separated)
-#   abext:M     tools/ab_extract.py over extraction modes M (A/B library)
+#   abext[:R]   tools/ab_extract.py: extraction timing at block resolution R (16; MQR_HIP_LIB picks the library)
 #   d2h         device -> host copy ceilings (tools/d2h_probe.py) with 1 / 4 / 8 staging threads
 #   chunkab     drop-in integrate() with 64- vs 127-frame hand-offs (tools/dropin_ab.py)
 #   conf        tools/conf_workload.py (the confidence kernel alone)
@@ -142,8 +142,9 @@ for step in ${STEPS:-tests}; do
       timeout -k 10 600 python -u tools/ab_integrate.py --check --rounds 7 --variants "${step#abint:}" \
         > gpurun_out/${TAG}_abint.json 2> gpurun_out/${TAG}_abint.err || { tail -20 gpurun_out/${TAG}_abint.err; exit 1; }
       cat gpurun_out/${TAG}_abint.json ;;
-    abext:*)
-      MQR_HIP_LIB="$PWD/tools/_ab/libmqr_ab.so" timeout -k 10 600 python -u tools/ab_extract.py --modes "${step#abext:}" --reps 21 \
+    abext|abext:*)
+      r=${step#abext}; r=${r#:}
+      timeout -k 10 600 python -u tools/ab_extract.py --block-resolution "${r:-16}" --reps 21 \
         > gpurun_out/${TAG}_abext.json 2> gpurun_out/${TAG}_abext.err || { tail -20 gpurun_out/${TAG}_abext.err; exit 1; }
       cat gpurun_out/${TAG}_abext.json ;;
     d2h)

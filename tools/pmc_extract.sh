@@ -13,7 +13,7 @@ for G in "${GROUPS_[@]}"; do
   i=$((i+1))
   rm -rf /tmp/pmcex/p$i
   timeout -s KILL 120 rocprofv3 --pmc $G -d /tmp/pmcex/p$i -o p --output-format csv -- \
-    python3 tools/ab_extract.py --modes 0 --reps 5 > gpurun_out/pmcex_p$i.log 2>&1 || { echo "group $i failed"; tail -3 gpurun_out/pmcex_p$i.log; exit 1; }
+    python3 tools/ab_extract.py --reps 5 > /tmp/pmcex_p$i.log 2>&1 || { echo "group $i failed"; tail -3 /tmp/pmcex_p$i.log; exit 1; }
 done
 python3 - <<'PY'
 import glob, json

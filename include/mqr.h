@@ -544,6 +544,37 @@ int mqr_edge_list_count(mqr_edge_list* list, int64_t* n);
 int mqr_edge_list_copy(mqr_edge_list* list, int32_t* pairs, int loc);
 int mqr_edge_list_free(mqr_edge_list* list);
 
+/* ---- surface samples (TriangleMesh.sample_points_uniformly, reconstruct_scene.py:151-171) ------------
+ * n area-weighted samples of a mesh's surface (csrc/meshsample.hip; the rule is this package's own, DESIGN
+ * §2.8: Open3D draws from std::mt19937, which is not matched).  vertices nv*3 float32, normals / colors
+ * nullable nv*3 float32, triangles nt*3 int32, all in `in_loc` memory (MQR_DEVICE buffers are read in place);
+ * out_positions n*3 float32 and the nullable out_normals / out_colors (n*3 float32) and out_triangle (n int32:
+ * the triangle each sample lies on), all in `out_loc` memory.  Sample i is a function of (mesh, seed, i)
+ * alone: a repeated call, another n, and host or device residency give identical bits.  Triangles are drawn
+ * in proportion to integer weights floor(area 2^(32 - e)) (largest area = m 2^e, m in [0.5, 1)), so a
+ * triangle below 2^-32 of the largest has weight 0 and is never drawn; the point is (wa a + wb b) + wc c in
+ * float64 with (wa, wb, wc) = (1 - s, s (1 - u2), s u2), s = sqrt(u1), rounded to float32; normals and colours
+ * take the same weights and are not renormalised; with use_triangle_normal the normal is the drawn triangle's
+ * unit normal instead (the vertex normals are then not read).  out_normals needs normals or
+ * use_triangle_normal, out_colors needs colors.  The work runs on the calling thread's caller stream
+ * (mqr_set_stream) and is complete on return.  n == 0 is a no-op.  Errors: nt == 0, n < 0, nt or nv >= 2^31,
+ * a non-finite coordinate, a triangle index outside [0, nv) (both found before any gather), every triangle
+ * degenerate (total weight zero; the outputs are then not written). */
+int mqr_mesh_sample_points(int device, const float* vertices, int64_t nv, const float* normals, const float* colors,
+                           const int32_t* triangles, int64_t nt, int in_loc, int64_t n, uint64_t seed,
+                           int use_triangle_normal, float* out_positions, float* out_normals, float* out_colors,
+                           int32_t* out_triangle, int out_loc);
+/* The two entries below are measurement hooks for tools/mesh_sample_probe.py, not for production callers
+ * (as mqr_color_frames_last_ms and mqr_vbg_set_variant are).
+ * last_ms: device time of the last completed call on `device`, ms, by events on the stream it ran on: the
+ * whole call (input checks and their host read included), the selection table (areas, weights, scan, coarse
+ * table), and the sample kernel.
+ * set_flat_search: non-zero makes the sample kernel search the whole prefix-sum table instead of the coarse
+ * table and one segment.  The samples are identical either way.  The setting is process-wide (an atomic
+ * word, read once by each call). */
+int mqr_mesh_sample_last_ms(int device, float* call_ms, float* table_ms, float* sample_ms);
+int mqr_mesh_sample_set_flat_search(int flat);
+
 /* Fragment registration (refine_fragment_poses.py:122-271): a CLOUD SET of N float32 xyz clouds in
  * HBM and three batched operations over pairs of them, standing in for Open3D's
  * evaluate_registration, multi_scale_icp (point to point) and get_information_matrix.

@@ -151,6 +151,11 @@ SIGNATURES = {
     "mqr_edge_list_count": (ctypes.c_int, [_vp, _i64p]),
     "mqr_edge_list_copy": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "mqr_edge_list_free": (ctypes.c_int, [_vp]),
+    "mqr_mesh_sample_points": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int, _vp, _vp,
+                                              _vp, _vp, ctypes.c_int]),
+    "mqr_mesh_sample_last_ms": (ctypes.c_int, [ctypes.c_int, _f32p, _f32p, _f32p]),
+    "mqr_mesh_sample_set_flat_search": (ctypes.c_int, [ctypes.c_int]),
     "mqr_vbg_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_vbg_set_variant": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_check_div64": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
@@ -285,6 +290,7 @@ ORDERED = frozenset({
     "mqr_cloudset_create", "mqr_cloudset_voxel_down", "mqr_evaluate_pairs", "mqr_icp_pairs", "mqr_information_pairs",
     "mqr_odometry_information_pairs", "mqr_colormap_create", "mqr_colormap_colors",
     "mqr_nn_create", "mqr_nn_query", "mqr_distance_stats", "mqr_mesh_measure", "mqr_edge_list_copy",
+    "mqr_mesh_sample_points",
 })
 _tls = threading.local()
 

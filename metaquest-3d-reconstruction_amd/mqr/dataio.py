@@ -476,10 +476,125 @@ class ImageDataIO:
             widths=np.full_like(timestamps, cam.width), heights=np.full_like(timestamps, cam.height))
 
 
+# ======================================================================================= reconstruction side
+class ReconstructionPaths:
+    """The result paths of the reference's ReconstructionPathConfig (config/project_path_config.py:229-247),
+    under its method names:
+
+        <project>/reconstruction/colorless_vbg.npz          the fused volume
+        <project>/reconstruction/colorless.ply              its point cloud
+        <project>/reconstruction/colorless_mesh_raw.ply     the extracted mesh
+        <project>/reconstruction/colorless_mesh_clean.ply   ... after the component filter
+        <project>/reconstruction/color_mesh.ply             the coloured mesh
+        <project>/reconstruction/color.ply                  the coloured point cloud sampled from it
+    """
+
+    def __init__(self, project_dir: Path):
+        self.project_dir = Path(project_dir).resolve()
+
+    def _result(self, name: str) -> Path:
+        return self.project_dir / "reconstruction" / name
+
+    def get_colorless_vbg_path(self) -> Path:
+        return self._result("colorless_vbg.npz")
+
+    def get_colorless_pcd_path(self) -> Path:
+        return self._result("colorless.ply")
+
+    def get_colorless_mesh_raw_path(self) -> Path:
+        return self._result("colorless_mesh_raw.ply")
+
+    def get_colorless_mesh_clean_path(self) -> Path:
+        return self._result("colorless_mesh_clean.ply")
+
+    def get_colored_mesh_path(self) -> Path:
+        return self._result("color_mesh.ply")
+
+    def get_colored_pcd_path(self) -> Path:
+        return self._result("color.ply")
+
+    def get_relative_path(self, path: Path) -> Path:
+        return path.relative_to(self.project_dir)
+
+
+class ReconstructionDataIO:
+    """The result writers of the reference's ReconstructionDataIO (scripts/dataio/reconstruction_data_io.py:
+    42-145) without Open3D: PLY files go through mqr.geometry's host writers (binary, Open3D's legacy layout;
+    colours as ``uchar red / green / blue`` when the geometry has them), the volume through
+    ``VoxelBlockGrid.save`` / ``load``.  `project_dir`: the capture directory, or a path object with
+    ReconstructionPaths' methods (the reference's ReconstructionPathConfig).  The ``_legacy`` writers take
+    what ``to_legacy()`` returns -- with or without Open3D installed -- or the tensor geometry itself; a
+    geometry held in HBM is copied to the host once, by the write."""
+
+    def __init__(self, project_dir):
+        self.reconstruction_path_config = (project_dir if hasattr(project_dir, "get_colored_pcd_path")
+                                           else ReconstructionPaths(project_dir))
+        self.paths = self.reconstruction_path_config
+
+    @staticmethod
+    def _ready(path: Path) -> str:
+        path.parent.mkdir(parents=True, exist_ok=True)
+        return str(path)
+
+    # -- the volume ------------------------------------------------------------------------
+    def load_colorless_vbg(self, device=None):
+        from .vbg import VoxelBlockGrid
+        path = self.paths.get_colorless_vbg_path()
+        if not path.exists():
+            return None
+        return VoxelBlockGrid.load(str(path), device=device)
+
+    def save_colorless_vbg(self, vbg):
+        vbg.save(self._ready(self.paths.get_colorless_vbg_path()))
+
+    # -- colourless geometry ---------------------------------------------------------------
+    def save_colorless_pcd_legacy(self, pcd):
+        from .geometry import write_point_cloud
+        write_point_cloud(self._ready(self.paths.get_colorless_pcd_path()), pcd, write_ascii=False, compressed=True)
+
+    def save_colorless_mesh_raw_legacy(self, mesh):
+        from .geometry import write_triangle_mesh
+        write_triangle_mesh(self._ready(self.paths.get_colorless_mesh_raw_path()), mesh)
+
+    def save_colorless_mesh_clean_legacy(self, mesh):
+        from .geometry import write_triangle_mesh
+        write_triangle_mesh(self._ready(self.paths.get_colorless_mesh_clean_path()), mesh)
+
+    # -- coloured geometry -----------------------------------------------------------------
+    def load_colored_mesh(self):
+        from .geometry import read_triangle_mesh
+        path = self.paths.get_colored_mesh_path()
+        return read_triangle_mesh(str(path)) if path.exists() else None
+
+    def save_colored_mesh_legacy(self, mesh):
+        from .geometry import write_triangle_mesh
+        write_triangle_mesh(self._ready(self.paths.get_colored_mesh_path()), mesh)
+
+    def save_colored_mesh(self, mesh):
+        self.save_colored_mesh_legacy(mesh)
+
+    def load_colored_pcd(self, device=None, print_progress: bool = True):
+        from .geometry import read_point_cloud
+        path = self.paths.get_colored_pcd_path()
+        if not path.exists():
+            return None
+        pcd = read_point_cloud(str(path))
+        return pcd if device is None else pcd.to(device)
+
+    def save_colored_pcd_legacy(self, pcd):
+        from .geometry import write_point_cloud
+        write_point_cloud(self._ready(self.paths.get_colored_pcd_path()), pcd, write_ascii=False, compressed=True)
+
+    def save_colored_pcd(self, pcd):
+        self.save_colored_pcd_legacy(pcd)
+
+
 class DataIO:
-    """The two sides of a capture directory: ``.depth`` (DepthDataIO) and ``.color`` (ImageDataIO)."""
+    """A capture directory: ``.depth`` (DepthDataIO), ``.color`` (ImageDataIO) and ``.reconstruction``
+    (ReconstructionDataIO, the results)."""
 
     def __init__(self, project_dir: Path):
         self.project_dir = Path(project_dir).resolve()
         self.depth = DepthDataIO(self.project_dir)
         self.color = ImageDataIO(self.project_dir)
+        self.reconstruction = ReconstructionDataIO(self.project_dir)

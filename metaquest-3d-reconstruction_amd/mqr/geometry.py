@@ -281,12 +281,20 @@ def _try_open3d():
         return None
 
 
-def _write_ply(path, verts, normals=None, tris=None):
+def color_to_uint8(colors) -> np.ndarray:
+    """Open3D's ColorToUint8 as recalled (VERIFY): ``floor(clamp(c, 0, 1) * 255 + 0.5)`` as uint8, in float64."""
+    c = np.clip(np.asarray(colors, np.float64), 0.0, 1.0)
+    return np.floor(c * 255.0 + 0.5).astype(np.uint8)
+
+
+def _write_ply(path, verts, normals=None, tris=None, colors=None):
     """Binary little-endian PLY in the layout Open3D's legacy writers use (``write_point_cloud`` /
-    ``write_triangle_mesh`` with ``write_ascii=False``, reference ``reconstruction_data_io.py:57-94``;
+    ``write_triangle_mesh`` with ``write_ascii=False``, reference ``reconstruction_data_io.py:57-145``;
     upstream FilePLY.cpp as recalled -- VERIFY): a ``comment Created by Open3D`` line, vertex
-    coordinates and normals as ``double`` (the legacy geometry holds float64), faces as a ``uchar``
-    count followed by ``uint`` indices.  The float32 device values widen to float64 exactly."""
+    coordinates and normals as ``double`` (the legacy geometry holds float64), then -- for geometry with
+    colours -- ``uchar red / green / blue`` (``color_to_uint8``), faces as a ``uchar`` count followed by
+    ``uint`` indices.  The float32 device values widen to float64 exactly.  Without colours the file is
+    byte for byte what it was before colours were supported."""
     verts = np.asarray(verts, np.float64).reshape(-1, 3)
     n = len(verts)
     props = ["property double x", "property double y", "property double z"]
@@ -294,13 +302,24 @@ def _write_ply(path, verts, normals=None, tris=None):
     if normals is not None and len(normals) == n:
         props += ["property double nx", "property double ny", "property double nz"]
         cols.append(np.asarray(normals, np.float64).reshape(-1, 3))
+    rgb = None
+    if colors is not None and len(colors) == n:
+        props += ["property uchar red", "property uchar green", "property uchar blue"]
+        rgb = color_to_uint8(colors).reshape(-1, 3)
     header = ["ply", "format binary_little_endian 1.0", "comment Created by Open3D", f"element vertex {n}"] + props
     if tris is not None:
         header += [f"element face {len(tris)}", "property list uchar uint vertex_indices"]
     header.append("end_header")
     with open(path, "wb") as f:
         f.write(("\n".join(header) + "\n").encode())
-        f.write(np.ascontiguousarray(np.concatenate(cols, axis=1), dtype="<f8").tobytes())
+        body = np.ascontiguousarray(np.concatenate(cols, axis=1), dtype="<f8")
+        if rgb is None:
+            f.write(body.tobytes())
+        else:
+            rec = np.empty(n, dtype=[("d", "<f8", (body.shape[1],)), ("c", "u1", (3,))])
+            rec["d"] = body
+            rec["c"] = rgb
+            f.write(rec.tobytes())
         if tris is not None:
             t = np.asarray(tris).reshape(-1, 3)
             if len(t) and (t.min() < 0 or t.max() >= max(n, 1)):
@@ -350,8 +369,10 @@ def read_ply(path):
 
 
 class PointCloud:
-    def __init__(self, positions, normals, device=None):
+    def __init__(self, positions, normals, device=None, colors=None):
         self.point = _AttrMap(positions=_tensor(positions), normals=_tensor(normals))
+        if colors is not None:
+            self.point["colors"] = _tensor(colors)
         self.device = device
 
     @classmethod
@@ -367,8 +388,19 @@ class PointCloud:
     def normals(self):
         return self.point.normals.numpy()
 
+    @property
+    def colors(self):
+        """The per-point colours (float32 in [0, 1]) as a host array, or None for a cloud without colours."""
+        c = self.point.get("colors")
+        return None if c is None else c.numpy()
+
+    def has_colors(self) -> bool:
+        return self.point.get("colors") is not None
+
     def cpu(self):
-        return PointCloud(self.point.positions.cpu(), self.point.normals.cpu(), device="CPU:0")
+        c = self.point.get("colors")
+        return PointCloud(self.point.positions.cpu(), self.point.normals.cpu(), device="CPU:0",
+                          colors=None if c is None else c.cpu())
 
     def to(self, device):
         self.device = device
@@ -381,17 +413,21 @@ class PointCloud:
         pcd = o3d.geometry.PointCloud()
         pcd.points = o3d.utility.Vector3dVector(self.points.astype(np.float64))
         pcd.normals = o3d.utility.Vector3dVector(self.normals.astype(np.float64))
+        if self.has_colors():
+            pcd.colors = o3d.utility.Vector3dVector(self.colors.astype(np.float64))
         return pcd
 
     def write_ply(self, path):
-        _write_ply(path, self.points, self.normals)
+        _write_ply(path, self.points, self.normals, colors=self.colors)
 
     def uniform_down_sample(self, every_k_points: int):
         """Points 0, k, 2k, ... (``o3d.t.geometry.PointCloud.uniform_down_sample``) as a host cloud."""
         k = int(every_k_points)
         if k < 1:
             raise ValueError("every_k_points must be >= 1")
-        return PointCloud(self.points[::k].copy(), self.normals[::k].copy(), device=self.device)
+        c = self.colors
+        return PointCloud(self.points[::k].copy(), self.normals[::k].copy(), device=self.device,
+                          colors=None if c is None else c[::k].copy())
 
     def voxel_down_sample(self, voxel_size: float):
         """Mean position per occupied voxel, in ascending voxel order, computed on the GPU
@@ -429,9 +465,21 @@ class TriangleMesh:
     def triangles(self):
         return self.triangle.indices.numpy()
 
+    @property
+    def vertex_colors(self):
+        """The per-vertex colours (``vertex["colors"]``, float32 in [0, 1]) as a host array, or None."""
+        c = self.vertex.get("colors")
+        return None if c is None else _tensor(c).numpy()
+
+    def has_vertex_colors(self) -> bool:
+        return self.vertex.get("colors") is not None
+
     def cpu(self):
-        return TriangleMesh(self.vertex.positions.cpu(), self.vertex.normals.cpu(), self.triangle.indices.cpu(),
+        mesh = TriangleMesh(self.vertex.positions.cpu(), self.vertex.normals.cpu(), self.triangle.indices.cpu(),
                             device="CPU:0")
+        if self.has_vertex_colors():
+            mesh.vertex["colors"] = _tensor(self.vertex["colors"]).cpu()
+        return mesh
 
     def to(self, device):
         self.device = device
@@ -445,43 +493,163 @@ class TriangleMesh:
         m.vertices = o3d.utility.Vector3dVector(self.vertices.astype(np.float64))
         m.vertex_normals = o3d.utility.Vector3dVector(self.vertex_normals.astype(np.float64))
         m.triangles = o3d.utility.Vector3iVector(self.triangles.astype(np.int32))
+        if self.has_vertex_colors():
+            m.vertex_colors = o3d.utility.Vector3dVector(self.vertex_colors.astype(np.float64))
         return m
 
     def write_ply(self, path):
-        _write_ply(path, self.vertices, self.vertex_normals, self.triangles)
+        _write_ply(path, self.vertices, self.vertex_normals, self.triangles, colors=self.vertex_colors)
+
+    def sample_points_uniformly(self, number_of_points: int, use_triangle_normal: bool = False, seed: int = 0):
+        """``number_of_points`` area-weighted samples of the surface as a :class:`PointCloud` (Open3D's
+        ``sample_points_uniformly``; reference ``reconstruct_scene.py:151-171``), drawn on the GPU
+        (csrc/meshsample.hip).  A mesh held in HBM is read in place and the cloud stays on its device; a host
+        mesh is sampled on ``parse_device(self.device)`` and the cloud comes back to the host.  The cloud
+        carries ``point.colors`` when the mesh has ``vertex["colors"]``; normals are the vertex normals under
+        the point's barycentric weights (not renormalised), or the triangle's unit normal with
+        ``use_triangle_normal``.
+
+        The rule is this package's own (DESIGN §2.8; Open3D's ``std::mt19937`` stream is not matched): sample
+        ``i`` depends on the mesh, ``seed`` and ``i`` alone, so calls with another ``number_of_points`` share
+        their first samples, and host and device meshes give identical bits.  ``RuntimeError`` for
+        ``number_of_points <= 0`` or a mesh without triangles (as Open3D), and for a mesh whose every triangle
+        is degenerate; ``ValueError`` for a non-finite coordinate, a triangle index out of range, or normals /
+        colours that are not shaped like the positions (checked on the host before anything is launched)."""
+        from . import _lib
+        from .vbg import parse_device
+        n = int(number_of_points)
+        if n <= 0:
+            raise RuntimeError("[sample_points_uniformly] number_of_points <= 0")
+        f = mesh_fields(self)
+        if int(np.prod(f.triangles.shape[:-1])) == 0 or int(np.prod(f.positions.shape[:-1])) == 0:
+            raise RuntimeError("[sample_points_uniformly] input mesh has no triangles")
+        seed = int(seed) & (2 ** 64 - 1)
+        d = device_mesh(f, normals=True, colors=True)
+        held = []  # device buffers of fields uploaded for this call
+
+        def upload(name, x, dev, nv):
+            # a field that is not usable in place (a host tensor, another dtype or device): the kernel gathers
+            # nv rows from it and the C ABI takes no length, so its shape is checked here, before any launch
+            rows = host_rows(x, np.float32)
+            if rows.shape != (nv, 3):
+                raise ValueError(f"vertex {name} must be {(nv, 3)}, got {rows.shape}")
+            held.append(_lib.DeviceBuffer.from_array(rows, dev))
+            return held[-1].ptr.value
+
+        try:
+            if d is not None:
+                dev, nv, nt, loc = d.device, d.nv, d.nt, _lib.MQR_DEVICE
+                pv, pt = d.positions, d.triangles
+                pn = (None if use_triangle_normal else d.normals if d.normals is not None
+                      else upload("normals", f.normals, dev, nv))
+                pc = (None if f.colors is None else d.colors if d.colors is not None
+                      else upload("colors", f.colors, dev, nv))
+            else:
+                dev, loc = parse_device(self.device), _lib.MQR_HOST
+                v, t = host_rows(f.positions, np.float32), np.asarray(host_array(f.triangles)).reshape(-1, 3)
+                if not np.isfinite(v).all():
+                    raise ValueError("a vertex coordinate is not finite")
+                if t.min() < 0 or t.max() >= len(v):
+                    raise ValueError(f"a triangle index is outside [0, {len(v)})")
+                t = np.ascontiguousarray(t, dtype=np.int32)
+                hn = None if use_triangle_normal else host_rows(f.normals, np.float32)
+                hc = None if f.colors is None else host_rows(f.colors, np.float32)
+                for name, x in (("normals", hn), ("colors", hc)):
+                    if x is not None and x.shape != v.shape:
+                        raise ValueError(f"vertex {name} must be {v.shape}, got {x.shape}")
+                nv, nt = len(v), len(t)
+                pv, pt = v.ctypes.data, t.ctypes.data
+                pn, pc = (None if x is None else x.ctypes.data for x in (hn, hc))
+            if d is not None:
+                outs = [_lib.DeviceBuffer(12 * n, dev) for _ in range(3 if pc is not None else 2)]
+                optr = [b.ptr.value for b in outs]
+                wrap = [Tensor(DeviceArray(b, b.ptr.value, (n, 3), np.float32, dev)) for b in outs]
+            else:
+                outs = [np.empty((n, 3), np.float32) for _ in range(3 if pc is not None else 2)]
+                optr = [a.ctypes.data for a in outs]
+                wrap = outs
+            vp = ctypes.c_void_p
+            try:
+                _lib.call("mqr_mesh_sample_points", int(dev), vp(pv), nv, vp(pn), vp(pc), vp(pt), nt, loc, n, seed,
+                          1 if use_triangle_normal else 0, vp(optr[0]), vp(optr[1]),
+                          vp(optr[2]) if pc is not None else None, None, loc)
+            except _lib.MqrError as e:
+                if "not finite" in str(e) or "outside [0" in str(e):
+                    raise ValueError(str(e)) from e
+                raise
+        finally:
+            for b in held:
+                b.free()
+        return PointCloud(wrap[0], wrap[1], device=self.device, colors=wrap[2] if pc is not None else None)
 
 
-# ---- o3d.io mirror for the reference's writers (reconstruction_data_io.py:57-94) -------------------
+# ---- o3d.io mirror for the reference's writers (reconstruction_data_io.py:57-145) ------------------
+def _colors_of(obj, attr):
+    """The colour array of a legacy-style geometry (``.colors`` / ``.vertex_colors``), or None when it has
+    none (``has_colors()`` / ``has_vertex_colors()`` honoured where the object has them; an empty array is none)."""
+    has = getattr(obj, "has_" + attr, None)
+    if callable(has) and not has():
+        return None
+    c = getattr(obj, attr, None)
+    if c is None:
+        return None
+    c = np.asarray(c)
+    return c if c.size else None
+
+
 def write_point_cloud(filename, pointcloud, write_ascii=False, compressed=False, print_progress=False):
     """``o3d.io.write_point_cloud`` for ``.ply`` (binary; ``compressed`` has no effect on PLY in
-    Open3D either).  Returns True like Open3D."""
+    Open3D either); a cloud with colours gets ``uchar red / green / blue``.  Returns True like Open3D."""
     if write_ascii:
         raise NotImplementedError("ASCII PLY is not written by the reference pipeline")
     if not str(filename).lower().endswith(".ply"):
         raise ValueError("only .ply is supported")
-    _write_ply(filename, pointcloud.points, pointcloud.normals)
+    _write_ply(filename, pointcloud.points, pointcloud.normals, colors=_colors_of(pointcloud, "colors"))
     return True
 
 
 def write_triangle_mesh(filename, mesh, write_ascii=False, compressed=False, write_vertex_normals=True,
                         write_vertex_colors=True, write_triangle_uvs=True, print_progress=False):
-    """``o3d.io.write_triangle_mesh`` for ``.ply`` meshes without colours (the colorless raw and
-    clean meshes, ``reconstruction_data_io.py:68-78``).  Returns True like Open3D."""
+    """``o3d.io.write_triangle_mesh`` for ``.ply`` meshes (the colorless raw and clean meshes and the
+    coloured mesh, ``reconstruction_data_io.py:68-101``): vertex colours are written when the mesh has them
+    and ``write_vertex_colors`` is set.  Returns True like Open3D."""
     if write_ascii:
         raise NotImplementedError("ASCII PLY is not written by the reference pipeline")
     if not str(filename).lower().endswith(".ply"):
         raise ValueError("only .ply is supported")
     normals = mesh.vertex_normals if write_vertex_normals else None
-    _write_ply(filename, mesh.vertices, normals, mesh.triangles)
+    colors = _colors_of(mesh, "vertex_colors") if write_vertex_colors else None
+    _write_ply(filename, mesh.vertices, normals, mesh.triangles, colors=colors)
     return True
 
 
-def read_triangle_mesh(filename):
-    """Read a PLY mesh written by ``write_triangle_mesh`` (or any binary PLY with x/y/z[, nx/ny/nz]
-    and triangle faces) back as a :class:`TriangleMesh` (float32 positions, int32 triangles)."""
-    props, faces = read_ply(filename)
+def _ply_vertex_fields(props):
     v = np.stack([props["x"], props["y"], props["z"]], 1).astype(np.float32)
     nrm = (np.stack([props["nx"], props["ny"], props["nz"]], 1).astype(np.float32) if "nx" in props
            else np.zeros_like(v))
+    col = None
+    if all(k in props for k in ("red", "green", "blue")):
+        col = (np.stack([props["red"], props["green"], props["blue"]], 1).astype(np.float64) / 255.0).astype(np.float32)
+    return v, nrm, col
+
+
+def read_triangle_mesh(filename):
+    """Read a PLY mesh written by ``write_triangle_mesh`` (or any binary PLY with x/y/z[, nx/ny/nz][, red/green/
+    blue] and triangle faces) back as a :class:`TriangleMesh` (float32 positions, int32 triangles; colours
+    ``uchar / 255`` as float32 in ``vertex["colors"]`` when the file has them)."""
+    props, faces = read_ply(filename)
+    v, nrm, col = _ply_vertex_fields(props)
     tris = (faces if faces is not None else np.zeros((0, 3))).astype(np.int32)
-    return TriangleMesh(v, nrm, tris)
+    mesh = TriangleMesh(v, nrm, tris)
+    if col is not None:
+        mesh.vertex["colors"] = Tensor(col)
+    return mesh
+
+
+def read_point_cloud(filename):
+    """Read a PLY point cloud written by ``write_point_cloud`` back as a :class:`PointCloud` (float32
+    positions and normals -- zeros when the file has none -- and colours ``uchar / 255`` as float32 when the
+    file has them)."""
+    props, _ = read_ply(filename)
+    v, nrm, col = _ply_vertex_fields(props)
+    return PointCloud(v, nrm, colors=col)

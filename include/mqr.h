@@ -239,9 +239,11 @@ int mqr_confidence_counts(int device, const float* depths, int depth_loc, int N,
                           int ref_end, int frame_range, double depth_max, double error_threshold, uint16_t* counts,
                           int* packed);
 /* Diagnostic: enable (1) / disable (0) / keep (-1) per-pair stage counting of mqr_confidence on this
- * device (a slower kernel build); 2 = a timing-only build without the tap loads (wrong maps); last4 (nullable) = the last counted call's (pixel, neighbour) pairs
- * with a valid reference pixel, and how many the float32 prefilter, the float64 band filter and the
- * float64 back-projection decided. */
+ * device (a slower kernel build).  4 = counting off and the branchy float32 prefilter stages forced: they
+ * are the path of frames whose byte offsets do not fit 32 bits, and this is the test hook that runs them
+ * on small frames (identical maps); 0 or 1 returns to the default stages.  Any other value is an error.
+ * last4 (nullable) = the last counted call's (pixel, neighbour) pairs with a valid reference pixel, and how
+ * many the float32 prefilter, the float64 band filter and the float64 back-projection decided. */
 int mqr_confidence_stats(int device, int enable, int64_t* last4);
 int mqr_pixel_error_map(int device, const float* ref_depth, const float* tgt_depth, int H, int W, const float* K_ref,
                         const float* K_tgt, const float* T_cw_ref, const float* T_cw_inv_tgt, const float* T_cw_tgt,
@@ -357,19 +359,18 @@ typedef struct mqr_stats {
  * every touch launch (two more on the touch stream); results in mqr_vbg_stats. */
 int mqr_vbg_profile(mqr_vbg* v, int enable);
 
-/* Test / tuning hooks.  mqr_vbg_set_variant: low byte = integrate kernel (0 default = the fast kernels
- * where their preconditions hold, 1 generic, 2 exact R-specialised, 4 lean with dword gathers; all bit-identical,
- * see launch_integrate in csrc/vbg.hip; any other value is rejected); bit 8 serialises touch and integrate, bit 9 keeps touch
- * order instead of longest-first, bit 10 uses 32-frame batches instead of 127 (bit 20: 64-frame
- * batches; bits 21 / 22 / 23: a first batch of 64 / 32 / 16 frames), bit 11 records
- * system-scope ordering events, bit 12 probes one table slot per new key in the batch touch (forces
- * the full-table undo-and-retry path; test hook), bits 13-15 are retired and rejected (a rejected
- * value returns non-zero, sets mqr_last_error and leaves the volume's configuration as it was), bit 16 gives the touch one stride-4 pixel per thread instead of two, bit 18 turns
- * off the speculative first-batch integrate (k_gate; A/B), bit 24 makes mqr_integrate_frames on device frames
- * drain its streams before returning (A/B), bit 25 makes mqr_vbg_reset wait for an integrate in flight
- * instead of swapping in the second table / pool set (A/B), bit 26 runs the default integrate without its LDS
- * table of (w, 1 / (w + 1)) (k_integrate_win instead of k_integrate_wt; A/B), bit 27 keeps k_integrate_wt's two
- * Markstein corrections of s / sdf_trunc where one is verified exact for the volume's sdf_trunc (A/B).
+/* Test hooks.  mqr_vbg_set_variant: low byte = integrate kernel (0 default = the fast kernels where their
+ * preconditions hold, 1 generic, 2 exact R-specialised, 4 lean with dword gathers; all bit-identical, see
+ * launch_integrate in csrc/vbg.hip).  Three bits each force a path that some input selects on its own, so
+ * that a test can reach it with ordinary frames:
+ *   bit 12  the batch touch probes one table slot per new key: the full-table undo-and-retry path (a batch
+ *           that fills the probe-limited table);
+ *   bit 26  k_integrate_win instead of the LDS-table kernel k_integrate_wt (a volume whose weight bound is
+ *           unknown, or above the table's capacity);
+ *   bit 27  k_integrate_wt keeps two Markstein corrections of s / sdf_trunc (an sdf_trunc for which one
+ *           correction is not verified exact).
+ * Every other value -- another low byte, or any other bit: the driver modes measured and retired, DESIGN.md
+ * §4.1 -- is rejected: non-zero return, mqr_last_error set, the volume's configuration left as it was.
  * mqr_check_division: exhaustive bit-pattern check of the division shortcuts used on device against
  * IEEE division (which=0: 1/b via rcp_rn, 1: a/b via div_rn, 2: a/b via the bare core, 3: 1/b via
  * rcp_nm, 4: 1/b via rcp_m, over float bit patterns [lo_bits, lo_bits+count) as b or a); returns

@@ -20,6 +20,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "device_block.hpp"
 #include "mqr_common.hpp"
 
 namespace mqr {
@@ -286,7 +287,6 @@ struct Stage32 {
     float Z, EZ, P, EP, uu, vv, Eu, Ev;  // (floor(uu), floor(vv) are recomputed in stage 2: registers)
     float2 ab, cd;
 };
-template <bool DIAG = false>  // DIAG (timing only, wrong results): no tap loads
 __device__ __forceinline__ Stage32 decide32_stage1(const float* __restrict__ tgt, int W, int H, float wm1, float hm1,
                                                    const ConfFrame& ft, const Pix32& px) {
     constexpr float u = 0x1p-24f;
@@ -337,11 +337,6 @@ __device__ __forceinline__ Stage32 decide32_stage1(const float* __restrict__ tgt
     r.vv = vv;
     r.Eu = Eu;
     r.Ev = Ev;
-    if (DIAG) {
-        r.ab = make_float2(1.0f + r.uu * 1e-30f, 1.0f);
-        r.cd = make_float2(1.0f, 1.0f + r.vv * 1e-30f);
-        return r;
-    }
     const float* row0 = tgt + (int64_t)v0 * W + u0;  // the two taps of a row in one 8-byte load
     __builtin_memcpy(&r.ab, row0, sizeof(float2));
     __builtin_memcpy(&r.cd, row0 + W, sizeof(float2));
@@ -506,7 +501,7 @@ __device__ inline int ref_point(const ConfFrame& fr, int u, int v, float dref, d
 // profiles/r04_ab_confidence_variants.json (the other instances would spill).  With SLP vectorisation,
 // 30 fewer VALU per two pairs but 76 VGPRs / 6 waves, it ran 7.4-7.8 ms: the loop's load latency, not
 // only its issue, counts.
-template <bool STATS, bool WIDE, bool DIAG = false, bool BF = false, bool NARROW = false, bool W8 = false>
+template <bool STATS, bool WIDE, bool BF = false, bool NARROW = false, bool W8 = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W8 ? 8 : 1, 8))) void k_confidence(const float* __restrict__ depths, int N, int H, int W,
                                                     const ConfFrame* __restrict__ fr, int ref_begin, int r,
                                                     double depth_max, double d2_max, double sd,
@@ -517,16 +512,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W8 ? 8 : 1,
     // measured no faster for G = 4 ... 64)
     const int rloc = blockIdx.y;
     const int ref = ref_begin + rloc;
-#ifndef MQR_CONF_XCD
-#define MQR_CONF_XCD 1
-#endif
     // XCD bands: workgroups go to the 8 XCDs round-robin, so tile bx of a row of tiles divisible by 8 is
     // remapped for XCD x to work on the x-th eighth of the image -- its neighbour taps then come from
     // one band of each neighbour frame (~25 MB of window / 8), which the XCD's own 4 MB L2 can hold,
     // instead of from the whole frames: 6.48-6.51 vs 7.01-7.10 ms, 6 alternating processes each,
-    // identical maps (profiles/r04_ab_confidence_variants.json r04r; MQR_CONF_XCD=0: the plain order)
+    // identical maps (profiles/r04_ab_confidence_variants.json r04r, against the plain order)
     unsigned bx = blockIdx.x;
-    if (MQR_CONF_XCD && (gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
+    if ((gridDim.x & 7u) == 0) bx = (bx & 7u) * (gridDim.x >> 3) + (bx >> 3);
     const int64_t p0 = (int64_t)bx * blockDim.x + threadIdx.x;
     if (!STATS && p0 >= HW) return;  // (STATS: the wave reductions below need every lane)
     const int64_t p = p0 < HW ? p0 : HW - 1;
@@ -585,7 +577,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(W8 ? 8 : 1,
                                                                                 (short)0, (int)fbytes, 0x00020000),
                                               W4, fbytes, W, H, fr[tt], px);
                 else
-                    return decide32_stage1<DIAG>(depths + (int64_t)tt * HW, W, H, wm1f, hm1f, fr[tt], px);
+                    return decide32_stage1(depths + (int64_t)tt * HW, W, H, wm1f, hm1f, fr[tt], px);
             };
             auto account = [&](const Stage32& st, int tt) {
                 bool valid, cons, dfr;
@@ -818,39 +810,27 @@ double d2_threshold(float thr) {
     std::memcpy(&d, &lo, sizeof d);
     return d;
 }
-constexpr int kConfDevices = 64;
 struct ConfCache {
     std::mutex mu;
     hipStream_t s = nullptr;
-    ConfFrame* dfr = nullptr;  // device frame parameters, grow-only
-    ConfFrame* hfr = nullptr;  // pinned staging
+    GrowBuf d_fr;              // device frame parameters
+    ConfFrame* hfr = nullptr;  // pinned staging, `cap` frames
     int cap = 0;
     bool stats = false;                 // mqr_confidence_stats: count pairs per deciding stage
-    bool diag = false;                  // mqr_confidence_stats enable = 2: no tap loads (timing only)
-    bool branchy = false;               // enable = 4: the branchy float32 stages (A/B; 3 = the default)
+    bool branchy = false;               // mqr_confidence_stats enable = 4: force the branchy float32 stages
     unsigned long long* dst = nullptr;  // device counters [4]
     int64_t last[4] = {0, 0, 0, 0};     // pairs, float32 prefilter, float64 filter, float64 back-projection
     // grow-only device staging of host-array calls (uploaded depths; conf + valid before their download):
     // a hipMalloc / hipFree pair of ~240 MB per 64-frame call cost more than the kernel
-    void* d_in = nullptr;
-    size_t d_in_cap = 0;
-    void* d_out = nullptr;
-    size_t d_out_cap = 0;
+    GrowBuf d_in, d_out;
 };
+ConfCache g_conf_cache[kMaxDevices];
 
-int grow(void** p, size_t* cap, size_t want) {
-    if (*cap >= want) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    if (hipMalloc(p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        return 1;
-    }
-    *cap = want;
-    return 0;
+int scratch_failed(const char* who) {
+    (void)hipGetLastError();
+    set_error(std::string(who) + ": device allocation failed");
+    return 1;
 }
-ConfCache g_conf_cache[kConfDevices];
 }  // namespace
 
 #ifndef MQR_SRC_TAG
@@ -869,7 +849,7 @@ int mqr_confidence(int device, const float* depths, int depth_loc, int N, int H,
     MQR_REQUIRE(depths && K && T_cw && T_cw_inv && conf && valid, "null argument");
     MQR_REQUIRE(N > 0 && H > 0 && W > 0, "bad shape");
     MQR_REQUIRE(ref_begin >= 0 && ref_end <= N && ref_begin <= ref_end, "bad reference frame range");
-    MQR_REQUIRE(device >= 0 && device < kConfDevices, "bad device");
+    MQR_REQUIRE(device >= 0 && device < kMaxDevices, "bad device");
     MQR_CHECK_HIP(hipSetDevice(device));
     const int nref = ref_end - ref_begin;
     if (nref == 0) return 0;
@@ -882,13 +862,12 @@ int mqr_confidence(int device, const float* depths, int depth_loc, int N, int H,
     ConfCache& cc = g_conf_cache[device];
     std::lock_guard<std::mutex> lock(cc.mu);
     if (!cc.s) MQR_CHECK_HIP(hipStreamCreateWithFlags(&cc.s, hipStreamNonBlocking));
+    MQR_REQUIRE(cc.d_fr.reserve(sizeof(ConfFrame) * N, sizeof(ConfFrame) * N) == hipSuccess,
+                "mqr_confidence: device allocation failed");
     if (cc.cap < N) {
-        if (cc.dfr) (void)hipFree(cc.dfr);
         if (cc.hfr) (void)hipHostFree(cc.hfr);
-        cc.dfr = nullptr;
         cc.hfr = nullptr;
         cc.cap = 0;
-        MQR_CHECK_HIP(hipMalloc(&cc.dfr, sizeof(ConfFrame) * N));
         MQR_CHECK_HIP(hipHostMalloc(&cc.hfr, sizeof(ConfFrame) * N, hipHostMallocDefault));
         cc.cap = N;
     }
@@ -914,30 +893,30 @@ int mqr_confidence(int device, const float* depths, int depth_loc, int N, int H,
         fr[i].wc0 = c0;
         fr[i].wmask = m;
     }
-    ConfFrame* dfr = cc.dfr;
+    ConfFrame* dfr = cc.d_fr.as<ConfFrame>();
     float* dd = nullptr;
     double* dconf = conf;
     int32_t* dvalid = valid;
     MQR_CHECK_HIP(hipMemcpyAsync(dfr, fr, sizeof(ConfFrame) * N, hipMemcpyHostToDevice, s));
     const float* dsrc = depths;
     if (depth_loc != MQR_DEVICE) {
-        MQR_REQUIRE(grow(&cc.d_in, &cc.d_in_cap, sizeof(float) * N * HW) == 0, "mqr_confidence: device allocation failed");
-        dd = static_cast<float*>(cc.d_in);
+        const size_t bd = sizeof(float) * N * HW;
+        MQR_REQUIRE(cc.d_in.reserve(bd, bd) == hipSuccess, "mqr_confidence: device allocation failed");
+        dd = cc.d_in.as<float>();
         if (copy_to_device(device, dd, depths, sizeof(float) * N * HW, s)) return 1;
         dsrc = dd;
     }
     if (out_loc != MQR_DEVICE) {
-        const size_t bc = (sizeof(double) * nref * HW + 255) & ~(size_t)255;
-        MQR_REQUIRE(grow(&cc.d_out, &cc.d_out_cap, bc + sizeof(int32_t) * nref * HW) == 0,
-                    "mqr_confidence: device allocation failed");
-        dconf = static_cast<double*>(cc.d_out);
-        dvalid = reinterpret_cast<int32_t*>(static_cast<char*>(cc.d_out) + bc);
+        const size_t bc = al256(sizeof(double) * nref * HW), bo = bc + sizeof(int32_t) * nref * HW;
+        MQR_REQUIRE(cc.d_out.reserve(bo, bo) == hipSuccess, "mqr_confidence: device allocation failed");
+        dconf = cc.d_out.as<double>();
+        dvalid = reinterpret_cast<int32_t*>(cc.d_out.as<char>() + bc);
     }
     const dim3 grid((unsigned)((HW + 255) / 256), nref);
     const bool wide = frame_range > 31;    // a window of more than 64 frames: chunked defer masks
     const bool narrow = frame_range <= 15;  // at most 32 frames: 32-bit defer masks
     // the branch-free float32 stages (default) address the frames with 32-bit byte offsets; the branchy
-    // ones (mode 4, the first round-4 form) remain for frames past that and for A/Bs
+    // ones are the path of frames past that (mqr_confidence_stats mode 4 forces them, for the tests)
     const bool bf = !cc.branchy && 4 * (HW + W) < (int64_t{1} << 31);
     auto launch = [&](auto kern, unsigned long long* st) {
         hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, dsrc, N, H, W, dfr, ref_begin, frame_range, depth_max, d2max,
@@ -947,17 +926,15 @@ int mqr_confidence(int device, const float* depths, int depth_loc, int N, int H,
         if (!cc.dst) MQR_CHECK_HIP(hipMalloc(&cc.dst, 4 * sizeof(unsigned long long)));
         MQR_CHECK_HIP(hipMemsetAsync(cc.dst, 0, 4 * sizeof(unsigned long long), s));
         if (bf)
-            wide ? launch(k_confidence<true, true, false, true>, cc.dst)
-                 : narrow ? launch(k_confidence<true, false, false, true, true>, cc.dst)
-                          : launch(k_confidence<true, false, false, true>, cc.dst);
+            wide ? launch(k_confidence<true, true, true>, cc.dst)
+                 : narrow ? launch(k_confidence<true, false, true, true>, cc.dst)
+                          : launch(k_confidence<true, false, true>, cc.dst);
         else
             wide ? launch(k_confidence<true, true>, cc.dst) : launch(k_confidence<true, false>, cc.dst);
-    } else if (cc.diag) {  // timing diagnostics only (wrong results): no tap loads
-        launch(k_confidence<false, false, true>, nullptr);
     } else if (bf) {
-        wide ? launch(k_confidence<false, true, false, true>, nullptr)
-             : narrow ? launch(k_confidence<false, false, false, true, true, true>, nullptr)
-                      : launch(k_confidence<false, false, false, true, false, true>, nullptr);
+        wide ? launch(k_confidence<false, true, true>, nullptr)
+             : narrow ? launch(k_confidence<false, false, true, true, true>, nullptr)
+                      : launch(k_confidence<false, false, true, false, true>, nullptr);
     } else {
         wide ? launch(k_confidence<false, true>, nullptr) : launch(k_confidence<false, false>, nullptr);
     }
@@ -980,12 +957,13 @@ int mqr_confidence(int device, const float* depths, int depth_loc, int N, int H,
 }
 
 int mqr_confidence_stats(int device, int enable, int64_t* last4) {
-    MQR_REQUIRE(device >= 0 && device < kConfDevices, "bad device");
+    MQR_REQUIRE(device >= 0 && device < kMaxDevices, "bad device");
+    MQR_REQUIRE(enable == -1 || enable == 0 || enable == 1 || enable == 4,
+                "mqr_confidence_stats: enable is -1 (read only), 0, 1 or 4");
     ConfCache& cc = g_conf_cache[device];
     std::lock_guard<std::mutex> lock(cc.mu);
     if (enable >= 0) {
         cc.stats = enable == 1;
-        cc.diag = enable == 2;
         cc.branchy = enable == 4;
     }
     if (last4)
@@ -997,10 +975,12 @@ int mqr_check_div64(int device, int mode, uint64_t seed, uint64_t count, double 
                     uint64_t* mismatches, double* first_bad) {
     MQR_REQUIRE(mismatches && first_bad && (mode == 0 || mode == 1) && b_lo > 0 && b_hi >= b_lo, "bad arguments");
     MQR_CHECK_HIP(hipSetDevice(device));
-    unsigned long long* dm = nullptr;
-    double* db = nullptr;
-    MQR_CHECK_HIP(hipMalloc(&dm, sizeof(unsigned long long)));
-    MQR_CHECK_HIP(hipMalloc(&db, 2 * sizeof(double)));
+    // scratch from the block cache: every return below releases it, after the null stream has drained
+    CachedBlock blk(device, 2 * 256);
+    unsigned long long* dm = (unsigned long long*)blk.take(sizeof(unsigned long long));
+    double* db = (double*)blk.take(2 * sizeof(double));
+    if (!dm || !db) return scratch_failed("mqr_check_div64");
+    StreamDrain drain{nullptr};
     MQR_CHECK_HIP(hipMemset(dm, 0, sizeof(unsigned long long)));
     MQR_CHECK_HIP(hipMemset(db, 0, 2 * sizeof(double)));
     const uint64_t chunk = 1ull << 28;
@@ -1013,8 +993,6 @@ int mqr_check_div64(int device, int mode, uint64_t seed, uint64_t count, double 
     unsigned long long m = 0;
     MQR_CHECK_HIP(hipMemcpy(&m, dm, sizeof m, hipMemcpyDeviceToHost));
     MQR_CHECK_HIP(hipMemcpy(first_bad, db, 2 * sizeof(double), hipMemcpyDeviceToHost));
-    (void)hipFree(dm);
-    (void)hipFree(db);
     *mismatches = m;
     return 0;
 }
@@ -1029,12 +1007,12 @@ int mqr_pixel_error_map(int device, const float* ref_depth, const float* tgt_dep
     ConfFrame fr[2] = {};
     fill_frame(K_ref, T_cw_ref, nullptr, NAN, H, W, 0.f, fr[0]);
     fill_frame(K_tgt, T_cw_tgt, T_cw_inv_tgt, NAN, H, W, 0.f, fr[1]);
-    ConfFrame* dfr = nullptr;
-    float *dr = nullptr, *dt = nullptr, *de = nullptr;
-    MQR_CHECK_HIP(hipMalloc(&dfr, sizeof(fr)));
-    MQR_CHECK_HIP(hipMalloc(&dr, sizeof(float) * HW));
-    MQR_CHECK_HIP(hipMalloc(&dt, sizeof(float) * HW));
-    MQR_CHECK_HIP(hipMalloc(&de, sizeof(float) * HW));
+    const size_t bm = sizeof(float) * HW;
+    CachedBlock blk(device, al256(sizeof(fr)) + 3 * al256(bm));
+    ConfFrame* dfr = (ConfFrame*)blk.take(sizeof(fr));
+    float *dr = (float*)blk.take(bm), *dt = (float*)blk.take(bm), *de = (float*)blk.take(bm);
+    if (!dfr || !dr || !dt || !de) return scratch_failed("mqr_pixel_error_map");
+    StreamDrain drain{nullptr};
     MQR_CHECK_HIP(hipMemcpy(dfr, fr, sizeof(fr), hipMemcpyHostToDevice));
     MQR_CHECK_HIP(hipMemcpy(dr, ref_depth, sizeof(float) * HW, hipMemcpyHostToDevice));
     MQR_CHECK_HIP(hipMemcpy(dt, tgt_depth, sizeof(float) * HW, hipMemcpyHostToDevice));
@@ -1042,10 +1020,6 @@ int mqr_pixel_error_map(int device, const float* ref_depth, const float* tgt_dep
                        de);
     MQR_CHECK_HIP(hipGetLastError());
     MQR_CHECK_HIP(hipMemcpy(err_out, de, sizeof(float) * HW, hipMemcpyDeviceToHost));
-    (void)hipFree(dfr);
-    (void)hipFree(dr);
-    (void)hipFree(dt);
-    (void)hipFree(de);
     return 0;
 }
 

@@ -105,11 +105,10 @@ struct FrameParams {
 
 void make_frame_params(const double* K, const double* T_wc, FrameParams* fp);
 
-constexpr int kMaxBatch = 127;        // frames per device batch (one bit each in the slot mask)
-// frames of a call's first batch (its touch runs before any integrate): a full batch -- a 64-frame
-// first batch starts the first integrate sooner but adds a launch (2.551 vs 2.499 ms per C2 step,
-// profiles/r04_ab_integrate.json)
-constexpr int kFirstBatch = kMaxBatch;
+// frames per device batch (one bit each in the slot mask); the first batch of a call is a full batch too --
+// a 64-frame first batch starts the first integrate sooner but adds a launch (2.551 vs 2.499 ms per C2
+// step, profiles/r04_ab_integrate.json)
+constexpr int kMaxBatch = 127;
 constexpr int kFrameCounterBase = 8;  // per-frame raw touch counts live at counters[8 + f]
 constexpr int kFreshBase = kFrameCounterBase + kMaxBatch;  // per-frame new (block, frame) marks
 // ints of one parity's counter set.  The 9 spare ints at its end are kept on purpose: they fix where the
@@ -139,26 +138,16 @@ struct mqr_vbg {
     // (hipEventDisableSystemFence): a default (system-scope) event makes the packet processor write
     // back and invalidate every XCD's L2 at the record -- ~20 us between consecutive integrate
     // launches, and the next kernel starts cold.  Only ev_host (the host's read of the batch
-    // counters through pinned memory) keeps the system-scope release.  sys_fence (variant bit
-    // 0x800) records the system-scope twins instead, for the A/B.
+    // counters through pinned memory) keeps the system-scope release.
     hipEvent_t ev_touch[2] = {nullptr, nullptr};
     hipEvent_t ev_int[2] = {nullptr, nullptr};
-    hipEvent_t ev_touch_sys[2] = {nullptr, nullptr};
-    hipEvent_t ev_int_sys[2] = {nullptr, nullptr};
     hipEvent_t ev_host[2] = {nullptr, nullptr};
-    bool sys_fence = false;
     bool int_pending[2] = {false, false};
     bool lpt_ready[2] = {false, false};  // k_lpt_order already enqueued behind this parity's touch
     bool ctr_clean[2] = {true, true};    // the parity's counters are zero (a reset cleared them)
-    bool spec_head = true;               // first batch of a call: integrate enqueued behind its touch (k_gate)
-    // mqr_integrate_frames on device frames returns once its last integrate is queued (the caller's stream
-    // waits for it; the volume's next user orders behind it on the device) instead of draining the streams
-    bool async_return = true;
     bool act_check = false;  // activate_ordered's table-full check is still to be read (activate_ordered_check)
     int64_t batch_n_max = 0;             // largest batch list seen (grid of a speculative integrate)
-    hipEvent_t touch_ev(int p) const { return sys_fence ? ev_touch_sys[p] : ev_touch[p]; }
-    hipEvent_t int_ev(int p) const { return sys_fence ? ev_int_sys[p] : ev_int[p]; }
-    // the event that last closed parity p's integrate on its stream: int_ev(p), or, while profiling,
+    // the event that last closed parity p's integrate on its stream: ev_int[p], or, while profiling,
     // that launch's timing end event (one event record between launches instead of two)
     hipEvent_t int_done[2] = {nullptr, nullptr};
 
@@ -177,14 +166,14 @@ struct mqr_vbg {
     // up to the batch's end; -1 unknown): the default kernel's LDS table of (w, 1 / (w + 1)) has this many
     // entries (k_integrate_wt; without a bound, or above kRtabMax, k_integrate_win runs).
     int64_t launch_wbound = -1;
-    bool rtab = true;  // variant bit 26 clears it (A/B)
+    bool rtab = true;  // variant bit 26 clears it (test hook: k_integrate_win)
     bool div1 = true;  // one-correction s / sdf_trunc where verified (strunc_one_correction_ok); bit 27 clears it
 
     // Second table / pool set.  mqr_vbg_reset while an integrate is still in flight swaps the sets instead of
     // ordering the clear behind that integrate: the next call's touch then overlaps the previous call's last
     // integrate.  set_ev marks, on stream2, the last integrate that used a set while it was
     // current; a set swapped back in is cleared behind it.  Kept only for volumes within kAltMaxBytes and
-    // while the device keeps a quarter of its HBM free; variant bit 25 turns the swap off.
+    // while the device keeps a quarter of its HBM free.
     struct VolSet {
         mqr::Table tab{};
         mqr::bmask_t* mask1 = nullptr;
@@ -196,7 +185,6 @@ struct mqr_vbg {
     } alt;
     hipEvent_t set_ev = nullptr;  // the current set's event (swapped with alt.ev)
     bool set_ev_live = false;
-    bool flip_reset = true;
     int64_t flips = 0;  // resets that swapped the sets (mqr_vbg_flips)
 
     int32_t* lists[2] = {nullptr, nullptr};  // batch slot lists, capacity list_cap each
@@ -217,26 +205,19 @@ struct mqr_vbg {
     int64_t ex_hint[3] = {0, 0, 0};  // last extraction's vertex / triangle / point counts (speculative capacity)
 
     int kernel_variant = 0;    // integrate kernel configuration (launch_integrate in vbg.hip), 1 = generic
-    bool pipelined = true;     // overlap touch(b+1) with integrate(b)
-    bool lpt_order = true;     // integrate blocks in longest-first order
     bool probe_one = false;    // batch touch probes one slot per new key (variant bit 0x1000, test hook)
-    int batch_frames = mqr::kMaxBatch;  // frames per device batch (A/B: 32, variant bit 0x400; 64, bit 20)
-    int first_batch_frames = mqr::kFirstBatch;  // frames of a call's first batch
     // profiling
-    int touch_ppt = 2;  // stride-4 pixels per k_touch thread (variant bit 16: one)
     int last_var = -1;        // integrate variant of the last launch, after fallbacks (mqr_vbg_last_kernel)
     const char* last_kname = "";  // its main kernel (mqr_vbg_last_kernel_name)
     bool profile = false;
     bool profile_touch = false;  // mqr_vbg_profile level 2: also time the touch launches
     std::vector<std::pair<hipEvent_t, hipEvent_t>> int_events, touch_events;
     std::vector<hipEvent_t> ev_pool;  // timing events, created once and reused (hipEventCreate per
-    size_t ev_used = 0;               // launch added ~0.1 ms to a 500-frame step); device-scope
-    bool ev_pool_sys = false;         // release unless sys_fence (then a pool of default events)
-    unsigned timing_event_flags() const { return sys_fence ? hipEventDefault : hipEventDisableSystemFence; }
+    size_t ev_used = 0;               // launch added ~0.1 ms to a 500-frame step); device-scope release
     hipEvent_t pooled_event() {
         if (ev_used == ev_pool.size()) {
             hipEvent_t e = nullptr;
-            if (hipEventCreateWithFlags(&e, timing_event_flags()) != hipSuccess) return nullptr;
+            if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return nullptr;
             ev_pool.push_back(e);
         }
         return ev_pool[ev_used++];

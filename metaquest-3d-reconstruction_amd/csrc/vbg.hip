@@ -8,7 +8,7 @@
 //   table  keys u64 / vals i32 / mask u64 x2 (batch parity), open addressing, capacity >= 2x live keys
 //   lists  slots touched by the current batch (appended once per batch, on first touch), x2
 //
-// Per batch of <= 127 frames (the first of a call a full batch too; variant bits 21-23 shorten it for A/Bs): k_touch
+// Per batch of <= 127 frames (the first of a call a full batch too): k_touch
 // (two stride-4 pixels per thread per frame, 4 ray samples,
 // hash insert, per-slot frame bitmask) -> host reads the batch counters (pool growth, empty-frame
 // error) -> k_integrate (one workgroup per touched block, every voxel applies that block's frames
@@ -384,7 +384,7 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
                             float depth_scale, float depth_max, float sdf_trunc, int first_new, int64_t spec = 0) {
     const int64_t n = spec > 0 ? spec : std::min<int64_t>(v->hctr(p)[kListCount], v->list_cap);
     if (n == 0) return 0;
-    hipStream_t s = v->pipelined ? v->stream2 : v->stream;
+    hipStream_t s = v->stream2;
     const unsigned grid = (unsigned)std::min<int64_t>(n, 8192);
     const int64_t* depth_frame = dframe_dev(v, p);
     const Table t = v->table(p);
@@ -395,22 +395,23 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
     // touch -- and an order enqueued behind it -- completed: integrate needs no device-side wait on
     // the touch stream, only for an order enqueued here, after that read.
     bool touch_wait = false;
-    bool gated_by_order = false;  // k_lpt_order filled the shadow counters (no k_gate launch)
-    if (v->lpt_order && n > 1) {  // on the touch stream: overlaps the previous integrate
+    // more than one block: the longest-first list, whose order kernel also filled the shadow counters
+    // (no k_gate launch); a single block is integrated from the touch's own list
+    const bool ordered = n > 1;
+    if (ordered) {  // on the touch stream: overlaps the previous integrate
         if (!v->lpt_ready[p]) {
             if (enqueue_lpt(v, p, nframes)) return 1;
             touch_wait = true;
         }
         list = v->lpt[p];
         lmask = reinterpret_cast<bmask_t*>(v->lpt[p] + v->list_cap);
-        gated_by_order = true;
     }
     v->lpt_ready[p] = false;
-    if (v->pipelined && (touch_wait || spec > 0)) {
-        MQR_CHECK_HIP(hipEventRecord(v->touch_ev(p), v->stream));
-        MQR_CHECK_HIP(hipStreamWaitEvent(s, v->touch_ev(p), 0));
+    if (touch_wait || spec > 0) {
+        MQR_CHECK_HIP(hipEventRecord(v->ev_touch[p], v->stream));
+        MQR_CHECK_HIP(hipStreamWaitEvent(s, v->ev_touch[p], 0));
     }
-    if (spec > 0 && !gated_by_order) {
+    if (spec > 0 && !ordered) {
         hipLaunchKernelGGL(k_gate, dim3(1), dim3(64), 0, s, v->ctr(p), v->shadow(p), nframes);
         MQR_CHECK_HIP(hipGetLastError());
     }
@@ -512,8 +513,8 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
         }
     }
     if (!v->profile) {
-        MQR_CHECK_HIP(hipEventRecord(v->int_ev(p), s));
-        v->int_done[p] = v->int_ev(p);
+        MQR_CHECK_HIP(hipEventRecord(v->ev_int[p], s));
+        v->int_done[p] = v->ev_int[p];
     }
     v->int_pending[p] = true;
     return 0;
@@ -606,18 +607,12 @@ static int touch_launch(mqr_vbg* v, int p, const float* dbase, int64_t HW, int H
     }
     // (measured and removed, profiles/r04_ab_integrate.json and DESIGN.md §4.1: a frame per workgroup
     // (k_touch_frame), a two-phase collect / claim touch, 8 frames per strip workgroup with one claim per
-    // (block, frame group))
-    hipStream_t ts = v->stream;
-    if (n > 0) {
-        if (v->touch_ppt == 1)
-            hipLaunchKernelGGL(k_touch<1>, dim3((n + 255) / 256, b), dim3(256), 0, ts, dbase, HW, H, W,
-                               v->d_fp[p], dframe_dev(v, p), depth_scale, depth_max, sdf_trunc, block_size, t, max_probe,
-                               alloc, v->ctr(p), v->pool_ctr(), v->pool_cap, v->bkeys, v->lists[p], v->list_cap);
-        else
-            hipLaunchKernelGGL(k_touch<2>, dim3((n + 511) / 512, b), dim3(256), 0, ts, dbase, HW, H, W,
-                               v->d_fp[p], dframe_dev(v, p), depth_scale, depth_max, sdf_trunc, block_size, t, max_probe,
-                               alloc, v->ctr(p), v->pool_ctr(), v->pool_cap, v->bkeys, v->lists[p], v->list_cap);
-    }
+    // (block, frame group), one stride-4 pixel per thread instead of two)
+    constexpr int kStrip = 256 * kTouchPPT;  // stride-4 pixels per workgroup
+    if (n > 0)
+        hipLaunchKernelGGL(k_touch, dim3((n + kStrip - 1) / kStrip, b), dim3(256), 0, v->stream, dbase, HW, H, W,
+                           v->d_fp[p], dframe_dev(v, p), depth_scale, depth_max, sdf_trunc, block_size, t, max_probe,
+                           alloc, v->ctr(p), v->pool_ctr(), v->pool_cap, v->bkeys, v->lists[p], v->list_cap);
     MQR_CHECK_HIP(hipGetLastError());
     if (v->profile_touch) {
         MQR_CHECK_HIP(hipEventRecord(e1, v->stream));
@@ -677,8 +672,7 @@ static int touch_batch_launch(mqr_vbg* v, int p, const float* dbase, int64_t HW,
         return 1;
     // the batch order is computed while the host waits for the counters (pool growth below only
     // rewrites buffer indices, which the order does not read)
-    if (v->lpt_order && enqueue_lpt(v, p, b)) return 1;
-    return 0;
+    return enqueue_lpt(v, p, b);
 }
 
 static int touch_batch_resolve(mqr_vbg* v, int p, const float* dbase, int64_t HW, int H, int W, int b,
@@ -691,8 +685,7 @@ static int touch_batch_resolve(mqr_vbg* v, int p, const float* dbase, int64_t HW
         if (touch_launch(v, p, dbase, HW, H, W, b, depth_scale, depth_max, sdf_trunc, block_size, v->table(p), 1,
                          v->tab.cap))
             return 1;
-        if (v->lpt_order && enqueue_lpt(v, p, b)) return 1;
-        if (resolve_pool_overflow(v, p)) return 1;
+        if (enqueue_lpt(v, p, b) || resolve_pool_overflow(v, p)) return 1;
         v->stats.table_retries += 1;
     }
     v->batch_new_max = std::max(v->batch_new_max, v->pool_count - ts.pool_before);
@@ -834,8 +827,6 @@ int mqr_vbg_create(float voxel_size, int block_resolution, int64_t block_count, 
                  hipSuccess &&
              hipEventCreateWithFlags(&v->ev_int[p], hipEventDisableTiming | hipEventDisableSystemFence) ==
                  hipSuccess &&
-             hipEventCreateWithFlags(&v->ev_touch_sys[p], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&v->ev_int_sys[p], hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&v->ev_host[p], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         set_error("mqr_vbg_create: device allocation failed");
@@ -873,7 +864,7 @@ int mqr_vbg_destroy(mqr_vbg* v) {
         if (v->d_fp[p]) (void)hipFree(v->d_fp[p]);
         if (v->h_fp[p]) (void)hipHostFree(v->h_fp[p]);
         if (v->d_depth[p]) (void)hipFree(v->d_depth[p]);
-        for (hipEvent_t e : {v->ev_touch[p], v->ev_int[p], v->ev_touch_sys[p], v->ev_int_sys[p], v->ev_host[p]})
+        for (hipEvent_t e : {v->ev_touch[p], v->ev_int[p], v->ev_host[p]})
             if (e) (void)hipEventDestroy(e);
     }
     for (hipEvent_t e : v->ev_pool) (void)hipEventDestroy(e);
@@ -972,9 +963,9 @@ int mqr_vbg_reset(mqr_vbg* v) {
     MQR_REQUIRE(v, "null volume");
     MQR_CHECK_HIP(hipSetDevice(v->device));
     uint32_t segs = 0x1f;  // every counter segment (k_reset_table)
-    const bool inflight = v->pipelined && (v->int_pending[0] || v->int_pending[1]);
+    const bool inflight = v->int_pending[0] || v->int_pending[1];
     bool flip = false;
-    if (inflight && v->flip_reset && ensure_alt(v, &flip)) return 1;
+    if (inflight && ensure_alt(v, &flip)) return 1;
     if (flip) {
         // an integrate of the current set is still in flight (mqr_integrate_frames on device frames returns
         // before it ends): mark the set's last reader on the integrate stream and swap in the other set,
@@ -1057,15 +1048,12 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
     if (v->wbound >= 0) v->wbound += (int64_t)valid.size();  // (an upper bound even if the call fails part-way)
     int rc = 0;
     int batch = 0;
-    // batches of up to batch_frames frames (127), the first of a call a full batch as well
-    // (first_batch_frames; variant bits 21-23 shorten it for A/Bs): its touch runs
+    // batches of up to kMaxBatch frames, the first of a call a full batch as well: its touch runs
     // before any integrate, the later ones behind the previous batch's integrate
-    const size_t nb = (size_t)std::max(1, std::min(v->batch_frames, kMaxBatch));
-    const size_t nb0 = (size_t)std::max(1, std::min(v->first_batch_frames, (int)nb));
     int b = 0;
     for (size_t s = 0; s < valid.size(); s += (size_t)b, ++batch) {
-        const int p = v->pipelined ? (batch & 1) : 0;
-        b = (int)std::min<size_t>(batch == 0 ? nb0 : nb, valid.size() - s);
+        const int p = batch & 1;
+        b = (int)std::min<size_t>(kMaxBatch, valid.size() - s);
         const int* idx = valid.data() + s;
         if (ensure_fp(v, b)) return 1;
         if (depth_loc != MQR_DEVICE && ensure_depth(v, b * HW)) return 1;
@@ -1092,7 +1080,7 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
         // The first batch of a call: its integrate is enqueued right behind its touch, gated on the
         // device by the touch's own counters (k_gate), so the GPU does not idle while the host reads
         // them.  Later batches' counters are read while the previous integrate runs anyway.
-        const bool spec = batch == 0 && v->spec_head && v->pipelined && !v->probe_one && v->batch_n_max > 0;
+        const bool spec = batch == 0 && !v->probe_one && v->batch_n_max > 0;
         if (!caller_ordered) {
             if (order_after_caller(v->device, v->stream, v->stream2)) return 2;
             caller_ordered = true;
@@ -1154,7 +1142,7 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
         }
         if (launch_integrate(v, p, dbase, HW, H, W, b, depth_scale, depth_max, sdf_trunc, (int)pool_before)) return 1;
     }
-    if (rc == 0 && depth_loc == MQR_DEVICE && v->async_return) {
+    if (rc == 0 && depth_loc == MQR_DEVICE) {
         // Device frames, no error: every batch's counters have been read (pool growth, empty frames), so
         // nothing is left to decide on the host -- return with the last integrate queued.  The caller's
         // stream waits for it (its next write to the frames is ordered after the library's reads); the
@@ -1369,32 +1357,21 @@ int mqr_vbg_unpack_weighted(mqr_vbg* v, const int32_t* union_keys, int64_t U, co
 int mqr_vbg_set_variant(mqr_vbg* v, int variant) {
     MQR_REQUIRE(v, "null volume");
     // checked before anything is applied: a rejected value leaves the configuration as it was
+    // (the measured and retired driver modes -- serial touch, touch order, shorter batches, system-scope
+    // events, a synchronous return, a reset without the set swap -- are recorded in DESIGN.md §4.1)
+    constexpr unsigned kAccepted = 0xffu | 0x1000u | 0x4000000u | 0x8000000u;
     const int kernel = variant & 0xff;
-    if ((kernel != 0 && kernel != 1 && kernel != 2 && kernel != 4) || (variant & 0xe000)) {
+    if ((kernel != 0 && kernel != 1 && kernel != 2 && kernel != 4) || ((unsigned)variant & ~kAccepted)) {
         set_error("integrate variant " + std::to_string(variant) +
-                  ": the low byte selects kernel 0, 1, 2 or 4, and bits 13-15 are retired");
+                  ": the low byte selects kernel 0, 1, 2 or 4, bits 12, 26 and 27 force a path, "
+                  "every other bit is retired");
         return 1;
     }
     if (sync_all(v)) return 1;
     v->kernel_variant = kernel;
-    v->pipelined = (variant & 0x100) == 0;  // bit 8: serialise touch and integrate (A/B of the overlap)
-    // (the integrate stream rather than the touch stream at the device's highest priority measured
-    // 2.592 vs 2.587 ms per step: removed)
-    // (the later batches' touches on a stream restricted to 32 / 64 / 128 CUs measured 3.07 / 2.72 /
-    // 2.61 vs 2.54-2.58 ms per step -- the overlapped touch barely slows the integrate: removed)
-    v->lpt_order = (variant & 0x200) == 0;  // bit 9: integrate in touch order instead of longest-first
-    // bit 10: 32-frame batches; bit 20: 64-frame batches (round 3) (A/Bs)
-    v->batch_frames = (variant & 0x400) ? 32 : (variant & 0x100000) ? 64 : kMaxBatch;
-    // bits 21 / 22 / 23: a first batch of 64 / 32 / 16 frames (A/B of the step head)
-    v->first_batch_frames = (variant & 0x200000) ? 64 : (variant & 0x400000) ? 32 : (variant & 0x800000) ? 16 : kFirstBatch;
-    v->sys_fence = (variant & 0x800) != 0;  // bit 11: system-scope ordering / timing events (A/B)
-    v->probe_one = (variant & 0x1000) != 0; // bit 12: force the full-table retry path (test hook)
-    v->touch_ppt = (variant & 0x10000) ? 1 : 2;  // bit 16: one stride-4 pixel per touch thread (A/B)
-    v->spec_head = (variant & 0x40000) == 0;     // bit 18: no speculative first-batch integrate (A/B)
-    v->async_return = (variant & 0x1000000) == 0; // bit 24: integrate_frames drains its streams before returning (A/B)
-    v->flip_reset = (variant & 0x2000000) == 0;   // bit 25: reset waits for an in-flight integrate (no set swap, A/B)
-    v->rtab = (variant & 0x4000000) == 0;         // bit 26: k_integrate_win instead of the LDS-table kernel (A/B)
-    v->div1 = (variant & 0x8000000) == 0;         // bit 27: the LDS-table kernel keeps two quotient corrections (A/B)
+    v->probe_one = (variant & 0x1000) != 0;  // bit 12: force the full-table retry path
+    v->rtab = (variant & 0x4000000) == 0;    // bit 26: k_integrate_win instead of the LDS-table kernel
+    v->div1 = (variant & 0x8000000) == 0;    // bit 27: the LDS-table kernel keeps two quotient corrections
     return 0;
 }
 
@@ -1434,16 +1411,9 @@ int mqr_vbg_profile(mqr_vbg* v, int enable) {
     // create the timing events now, outside any timed region (more are created on demand until the
     // next stats read recycles them)
     MQR_CHECK_HIP(hipSetDevice(v->device));
-    if (v->profile && v->ev_pool_sys != v->sys_fence) {  // the fence scope changed: rebuild the pool
-        if (sync_all(v)) return 1;
-        drain_events(v);
-        for (hipEvent_t e : v->ev_pool) (void)hipEventDestroy(e);
-        v->ev_pool.clear();
-        v->ev_pool_sys = v->sys_fence;
-    }
     while (v->profile && v->ev_pool.size() < 12288) {
         hipEvent_t e = nullptr;
-        MQR_CHECK_HIP(hipEventCreateWithFlags(&e, v->timing_event_flags()));
+        MQR_CHECK_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
         v->ev_pool.push_back(e);
     }
     return 0;

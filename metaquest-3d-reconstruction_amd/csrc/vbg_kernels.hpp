@@ -180,10 +180,10 @@ __device__ inline void wave_add(int* ctr, int v) {
 }
 
 // ------------------------------------------------------------------ kernels
-// compute_unique_block_coordinates for a batch: blockIdx.y = batch frame (bit), PPT stride-4 pixels
-// per thread (a workgroup covers 256 PPT consecutive ones), 4 samples each over
+// compute_unique_block_coordinates for a batch: blockIdx.y = batch frame (bit), kTouchPPT stride-4 pixels
+// per thread (a workgroup covers 256 times as many consecutive ones), 4 samples each over
 // [max(d - trunc, 0), min(d + trunc, depth_max)] (Appendix A.2).
-template <int PPT>
+constexpr int kTouchPPT = 2;  // (one pixel per thread was measured and retired)
 __global__ __launch_bounds__(256) void k_touch(const float* __restrict__ depths, int64_t HW, int H, int W,
                                                const FrameParams* __restrict__ fps,
                                                const int64_t* __restrict__ depth_frame, float depth_scale,
@@ -195,10 +195,10 @@ __global__ __launch_bounds__(256) void k_touch(const float* __restrict__ depths,
     // occurrences are collected in LDS and then claimed all at once, one per thread: each claim is a
     // chain of device-coherent round trips (probe, mask read, atomicOr, list append; ~2 200 cycles
     // per L2 read in this kernel), and claiming per sample left four such chains in sequence.  With
-    // PPT > 1 a workgroup covers a longer strip: the touch is latency-bound and holds its wave slots
+    // two pixels per thread a workgroup covers a longer strip: the touch is latency-bound and holds its wave slots
     // (taken from the overlapped integrate) for about one claim round, so fewer, longer-lived
     // workgroups with better deduplication hold fewer slot-microseconds.
-    constexpr int kSeen = 1024 * PPT;  // >= the 4 x 256 x PPT keys a workgroup can produce: never full
+    constexpr int kSeen = 1024 * kTouchPPT;  // >= the 4 x 256 x kTouchPPT keys a workgroup can produce: never full
     __shared__ unsigned long long seen[kSeen];
     __shared__ uint16_t uniq[kSeen];  // seen-slots of the first occurrences (LDS: workgroups per CU)
     __shared__ int wg_count[3];  // valid samples, new frame bits (one global atomic each), first keys
@@ -209,17 +209,17 @@ __global__ __launch_bounds__(256) void k_touch(const float* __restrict__ depths,
     const FrameParams& fp = fps[f];
     const int cols = W / 4, rows = H / 4, n = rows * cols;
     const float* __restrict__ dep = depths + depth_frame[f] * HW;
-    int wpx[PPT];
-    float dd[PPT];
+    int wpx[kTouchPPT];
+    float dd[kTouchPPT];
 #pragma unroll
-    for (int jp = 0; jp < PPT; ++jp) {  // all of the thread's depth reads in flight together
-        const int w = (blockIdx.x * PPT + jp) * blockDim.x + threadIdx.x;
+    for (int jp = 0; jp < kTouchPPT; ++jp) {  // all of the thread's depth reads in flight together
+        const int w = (blockIdx.x * kTouchPPT + jp) * blockDim.x + threadIdx.x;
         wpx[jp] = w;
         dd[jp] = w < n ? dep[(int64_t)((w / cols) * 4) * W + (w % cols) * 4] : 0.f;
     }
     int valid = 0, fresh = 0;
 #pragma unroll
-    for (int jp = 0; jp < PPT; ++jp) {
+    for (int jp = 0; jp < kTouchPPT; ++jp) {
         const int w = wpx[jp];
         uint64_t key[4] = {kEmpty, kEmpty, kEmpty, kEmpty};
         if (w < n) {

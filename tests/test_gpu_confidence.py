@@ -81,9 +81,22 @@ def test_confidence_band_edges_vs_oracle(thr, dmax):
         assert valid.max() > 0 and 0 < conf.mean() < 1
 
 
+def _branchy_maps(*args):
+    """confidence_maps with the branchy float32 stages forced (mqr_confidence_stats mode 4): the path of
+    frames whose byte offsets do not fit 32 bits, which no frame of test size takes on its own."""
+    from mqr import _lib
+    from mqr.confidence import confidence_maps
+    _lib.call("mqr_confidence_stats", 0, 4, None)
+    try:
+        return confidence_maps(*args)
+    finally:
+        _lib.call("mqr_confidence_stats", 0, 0, None)
+
+
 def test_confidence_float32_prefilter_stages_and_static_camera():
     """The float32 prefilter (pixel_decide32) decides most pairs and defers the uncertain ones: the
-    stage counts add up, the maps are identical with counting on or off, and a static camera (every
+    stage counts add up, the maps are identical with counting on or off and with the branchy stages
+    forced (bit for bit), and a static camera (every
     neighbour's projection lands exactly on integer pixel coordinates: every floor() is uncertain in
     float32, so every pair must take the float64 path) still matches the oracle bit for bit."""
     import ctypes
@@ -103,6 +116,8 @@ def test_confidence_float32_prefilter_stages_and_static_camera():
     pairs, f32, f64, tail = (int(x) for x in last)
     assert pairs > 0 and f32 + f64 + tail == pairs and f64 >= 0
     assert f32 > 0.9 * pairs, last
+    branchy = _branchy_maps(seq["depth"], seq["K"], seq["T_cw"], Ti, 0, 12, 10, 4.0, 0.08)
+    assert np.array_equal(base[0].view(np.uint64), branchy[0].view(np.uint64)) and np.array_equal(base[1], branchy[1])
     # static camera: all poses equal (noise differs per frame)
     T = np.repeat(seq["T_cw"][:1], 6, axis=0).astype(np.float32)
     Ts = np.linalg.inv(T.astype(np.float64)).astype(np.float32)
@@ -128,3 +143,5 @@ def test_confidence_wide_window_vs_oracle():
         assert np.array_equal(valid[i], ov), i
         assert np.array_equal(conf[i], oc), i
     assert valid.max() > 0  # (ref frame 35 reads a 70-frame window: two 64-neighbour chunks)
+    bconf, bvalid = _branchy_maps(seq["depth"], seq["K"], seq["T_cw"], Ti, 0, 70, 40, 4.0, 0.08)
+    assert np.array_equal(conf.view(np.uint64), bconf.view(np.uint64)) and np.array_equal(valid, bvalid)

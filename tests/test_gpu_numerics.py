@@ -45,17 +45,15 @@ def test_shortened_reciprocals_exact(which, lo, hi):
     assert mm == 0, f"mode {which}: {mm} mismatches, first bit pattern {first:#x}"
 
 
-# 0x10000: one pixel per touch thread, 0x40000: no speculative first-batch integrate, 0x100000: 64-frame
-# batches, 0x200000 / 0x400000 / 0x800000: a first batch of 64 / 32 / 16 frames, 0x4000000: the default
-# kernel without its LDS weight table (k_integrate_win)
-INTEGRATE_VARIANTS = {16: (0, 2, 4, 0x100, 0x104, 0x200, 0x400, 0x800, 0x10000, 0x40000, 0x100000, 0x200000,
-                           0x400000, 0x800000, 0x4000000, 0x8000000),
-                      8: (0, 2, 0x100)}
+# 0x4000000: the default kernel without its LDS weight table (k_integrate_win), 0x8000000: the LDS-table
+# kernel with two quotient corrections (k_integrate_wt<7, 0>)
+INTEGRATE_VARIANTS = {16: (0, 2, 4, 0x4000000, 0x8000000),
+                      8: (0, 2)}
 
 def test_specialised_integrate_equals_generic():
-    """Every integrate-kernel variant (lean default, LDS block-tiled, exact R-specialised; pipelined or
-    serial touch, longest-first or touch order, 64- or 32-frame batches) equals the generic kernel
-    (variant 1) bit for bit."""
+    """Every integrate-kernel variant (default, exact R-specialised, lean with dword gathers, the default
+    without its weight table or with two quotient corrections) equals the generic kernel (variant 1) bit
+    for bit."""
     from gpu_helpers import compare_volumes
     from mqr import _lib, synthetic
     from mqr.vbg import VoxelBlockGrid
@@ -201,7 +199,7 @@ def test_fast_integrate_exact_fallback():
     for d in depth_mm:
         d[::7, ::5] = np.float32(1e-30)   # in-image, > 0, below 2^-60: exact division path
     out = []
-    cases = ((16, 1), (16, 0), (16, 2), (16, 0x100), (8, 1), (8, 0), (8, 2))
+    cases = ((16, 1), (16, 0), (16, 2), (8, 1), (8, 0), (8, 2))
     for R, variant in cases:
         v = VoxelBlockGrid(voxel_size=0.01, block_resolution=R, block_count=64)
         _lib.call("mqr_vbg_set_variant", v.handle, variant)
@@ -215,10 +213,10 @@ def test_fast_integrate_exact_fallback():
         v.integrate_frames(depth_mm[4:], seq["K"][4:], seq["T_wc"][4:], depth_scale=1000.0, depth_max=4.0,
                            trunc_voxel_multiplier=10.0)
         out.append(v.export())
-    for i in (1, 2, 3):
+    for i in (1, 2):
         assert compare_volumes(out[0], out[i], 0.0) == 0.0, cases[i]
-    for i in (5, 6):
-        assert compare_volumes(out[4], out[i], 0.0) == 0.0, cases[i]
+    for i in (4, 5):
+        assert compare_volumes(out[3], out[i], 0.0) == 0.0, cases[i]
 
 
 def test_division_core_on_positive_zero():
@@ -243,8 +241,7 @@ def test_lean_integrate_exact_fallback():
     Ts = np.concatenate([np.eye(4)[None], seq["T_wc"]])
     # (k_integrate_win redoes such blocks in-kernel; the default's LDS-table kernel and variant 4 hand them
     # to the fix-up launch)
-    cases = ((16, 1), (16, 0), (16, 0x200), (16, 2), (16, 0x100), (16, 0x400),
-             (16, 0x800), (16, 0x100), (16, 0x200), (16, 4),
+    cases = ((16, 1), (16, 0), (16, 2), (16, 4),
              (8, 1), (8, 0), (8, 2))
     out = []
     for R, variant in cases:
@@ -261,10 +258,10 @@ def test_lean_integrate_exact_fallback():
         v.import_blocks(keys, tsdf, wgt)
         v.integrate_frames(depths[3:], Ks[3:], Ts[3:], depth_scale=1.0, depth_max=4.0, trunc_voxel_multiplier=10.0)
         out.append(v.export())
-    for i in range(1, 10):
+    for i in (1, 2, 3):
         assert compare_volumes(out[0], out[i], 0.0) == 0.0, cases[i]
-    for i in (11, 12):
-        assert compare_volumes(out[10], out[i], 0.0) == 0.0, cases[i]
+    for i in (5, 6):
+        assert compare_volumes(out[4], out[i], 0.0) == 0.0, cases[i]
 
 
 @pytest.mark.parametrize("mode,a_max,b_lo,b_hi", [
@@ -319,9 +316,10 @@ def test_weight_table_across_calls_and_unknown_bounds():
 
 
 def test_retired_integrate_variants_rejected():
-    """The low byte of mqr_vbg_set_variant selects kernel 0, 1, 2 or 4 and bits 13-15 are retired: any other
-    value is refused with a message and leaves the volume on its configuration -- the integrate that follows
-    runs the default (mqr_vbg_last_kernel 0) and equals the generic kernel bit for bit."""
+    """The low byte of mqr_vbg_set_variant selects kernel 0, 1, 2 or 4 and only bits 12, 26 and 27 are
+    accepted above it (the retired driver modes: bits 8-11, 13-16, 18, 20-25; never assigned: 17, 19, 28-31):
+    any other value is refused with a message and leaves the volume on its configuration -- the integrate
+    that follows runs the default (mqr_vbg_last_kernel 0) and equals the generic kernel bit for bit."""
     from gpu_helpers import compare_volumes
     from mqr import _lib, synthetic
     from mqr.vbg import VoxelBlockGrid
@@ -332,7 +330,8 @@ def test_retired_integrate_variants_rejected():
     _lib.call("mqr_vbg_set_variant", ref.handle, 1)
     ref.integrate_frames(seq["depth"], seq["K"], seq["T_wc"], **kw)
     ref_out = ref.export()
-    for variant in (3, 5, 44, 64, 0x2000, 0x4000, 0x8000):
+    for variant in (3, 5, 44, 64, 0x2000, 0x4000, 0x8000, 0x100, 0x200, 0x400, 0x800, 0x10000, 0x40000, 0x100000,
+                    0x200000, 0x400000, 0x800000, 0x1000000, 0x2000000, 0x20000, 0x80000, 0x10000000):
         v = VoxelBlockGrid(voxel_size=0.02, block_resolution=16, block_count=64)
         assert L.mqr_vbg_set_variant(v.handle, variant) != 0, hex(variant)
         assert L.mqr_last_error().decode(errors="replace").strip(), hex(variant)

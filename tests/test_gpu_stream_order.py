@@ -239,25 +239,6 @@ def test_reset_extract_and_second_call_after_an_unfinished_integrate():
     assert mesh.triangles.shape[0] == otri.shape[0]
 
 
-def test_synchronous_return_variant_is_identical():
-    """Variant bit 24 (the A/B of the asynchronous return) drains the streams before returning: same volume."""
-    import torch
-    from mqr import _lib
-    from mqr.vbg import VoxelBlockGrid
-    depth, K, T = _room(60, seed=13)
-    B, H, W = depth.shape
-    t = torch.from_numpy(depth).cuda()
-    torch.cuda.synchronize()
-    out = []
-    for variant in (0, 0x1000000):
-        vbg = VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=256, device="cuda:0")
-        _lib.call("mqr_vbg_set_variant", vbg.handle, variant)
-        vbg.integrate_frames((_Dev(t), B, H, W), K, T, depth_scale=1.0, depth_max=4.0, trunc_voxel_multiplier=10.0)
-        out.append(vbg.export())
-    from gpu_helpers import compare_volumes
-    assert compare_volumes(out[0], out[1], 0.0) == 0.0  # (block order is the touch's arrival order)
-
-
 def test_device_buffer_freed_right_after_integrate_frames():
     """A library-allocated frame buffer (mqr_device_alloc) freed the moment integrate_frames returns:
     mqr_device_free waits for the device, so the in-flight integrate still reads the frames."""
@@ -280,10 +261,9 @@ def _flips(vbg):
     return n.value
 
 
-@pytest.mark.parametrize("variant", [0, 0x2000000])
-def test_reset_behind_an_unfinished_integrate_swaps_sets(variant):
-    """reset while an integrate is in flight swaps in the volume's second table / pool set instead of waiting
-    (variant 0; bit 25 waits).  The calls alternate a long and a short sequence with no synchronize, so each
+def test_reset_behind_an_unfinished_integrate_swaps_sets():
+    """reset while an integrate is in flight swaps in the volume's second table / pool set instead of
+    waiting.  The calls alternate a long and a short sequence with no synchronize, so each
     reset finds the previous call's last integrate running: a set swapped back in must be cleared only after
     the integrate that last read it (the long one, two calls earlier), and the second set -- allocated at the
     capacities of the first, which grows in the first call -- must be replaced when the first grows past it.
@@ -292,7 +272,6 @@ def test_reset_behind_an_unfinished_integrate_swaps_sets(variant):
     import torch
     from gpu_helpers import compare_volumes
     from mqr.vbg import VoxelBlockGrid
-    from mqr import _lib
     d1, K1, T1 = _room(254, seed=21)
     d2, K2, T2 = _room(90, seed=22)
     B1, H, W = d1.shape
@@ -302,7 +281,6 @@ def test_reset_behind_an_unfinished_integrate_swaps_sets(variant):
     a = (_Dev(t1), B1, H, W), K1, T1
     b = (_Dev(t2), len(d2), H, W), K2, T2
     vbg = VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=64, device="cuda:0")
-    _lib.call("mqr_vbg_set_variant", vbg.handle, variant)
     for frames, K, T in (a, b, a, b, a):  # resets 2-5 each behind the previous call's unfinished integrate
         vbg.reset()
         vbg.integrate_frames(frames, K, T, **kw)
@@ -321,10 +299,7 @@ def test_reset_behind_an_unfinished_integrate_swaps_sets(variant):
     assert compare_volumes(vbg.export(), ref1.export(), 0.0) == 0.0
     assert vbg.capacity() >= cap
     flips = _flips(vbg)
-    if variant:
-        assert flips == 0
-    else:
-        assert flips == 5, flips  # 4 in the loop + the one behind the short call
+    assert flips == 5, flips  # 4 in the loop + the one behind the short call
     del ref2
 
 

@@ -199,25 +199,19 @@ def test_sharded_merge_matches_single_pass(mqr_mod, room_seq):
 def test_speculative_first_batch_gate(mqr_mod, room_seq):
     """The first batch of a call is integrated right behind its touch, gated on the device by the
     touch's counters (k_gate).  A volume that has integrated before (so the gate path is taken) gives
-    the same volume with the speculative head on and off (variant bit 18); a first batch whose pool
-    overflows (capacity 1 block) or holds a frame that touches nothing falls back to the ordinary path:
-    the result equals the oracle's and the error is raised as upstream does."""
-    from mqr import _lib
+    the oracle's volume; a first batch whose pool overflows (capacity 1 block) or holds a frame that
+    touches nothing falls back to the ordinary path: the result equals the oracle's and the error is
+    raised as upstream does."""
     K = room_seq["K"].astype(np.float64)
     T = room_seq["T_wc"].astype(np.float64)
     d = room_seq["depth"]
     kw = dict(depth_scale=1.0, depth_max=4.0, trunc_voxel_multiplier=10.0)
-    vols = []
-    for variant in (0, 0x40000):
-        v = mqr_mod.VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=4096)
-        _lib.call("mqr_vbg_set_variant", v.handle, variant)
-        v.integrate_frames(d[:4], K[:4], T[:4], **kw)  # sets the speculative grid estimate
-        v.reset()
-        v.integrate_frames(d, K, T, **kw)
-        vols.append(v)
-    assert compare_volumes(vols[0].export(), vols[1].export(), 0.0) == 0.0
+    vol = mqr_mod.VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=4096)
+    vol.integrate_frames(d[:4], K[:4], T[:4], **kw)  # sets the speculative grid estimate
+    vol.reset()
+    vol.integrate_frames(d, K, T, **kw)
     ref = _oracle_run(room_seq, 0.01, 16, 4.0, 10.0)
-    compare_volumes(vols[0].export(), ref.export(), 0.0)
+    compare_volumes(vol.export(), ref.export(), 0.0)
     # pool overflow inside the speculative first batch: capacity 1 block
     small = mqr_mod.VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=1)
     small.integrate_frames(d[:1], K[:1], T[:1], **kw)
@@ -227,10 +221,18 @@ def test_speculative_first_batch_gate(mqr_mod, room_seq):
     # a frame that touches nothing inside the first batch: frames before it integrated, then the error
     dd = d.copy()
     dd[3] = 0.0
-    vols[0].reset()
+    vol.reset()
     with pytest.raises(RuntimeError, match="No block is touched"):
-        vols[0].integrate_frames(dd, K, T, **kw)
-    compare_volumes(vols[0].export(), _oracle_run(room_seq, 0.01, 16, 4.0, 10.0, frames=[0, 1, 2]).export(), 0.0)
+        vol.integrate_frames(dd, K, T, **kw)
+    compare_volumes(vol.export(), _oracle_run(room_seq, 0.01, 16, 4.0, 10.0, frames=[0, 1, 2]).export(), 0.0)
+
+
+def _last_kernel_name(vbg):
+    import ctypes
+    from mqr import _lib
+    buf = ctypes.create_string_buffer(64)
+    _lib.call("mqr_vbg_last_kernel_name", vbg.handle, buf, 64)
+    return buf.value.decode()
 
 
 def test_released_grid_is_reused_as_a_new_one(mqr_mod, room_seq):
@@ -244,14 +246,16 @@ def test_released_grid_is_reused_as_a_new_one(mqr_mod, room_seq):
     T = room_seq["T_wc"].astype(np.float64)
     kw = dict(depth_scale=1.0, depth_max=4.0, trunc_voxel_multiplier=10.0)
     a = mqr_mod.VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=4096)
-    _lib.call("mqr_vbg_set_variant", a.handle, 0x400)  # 32-frame batches: must not carry over
+    _lib.call("mqr_vbg_set_variant", a.handle, 0x4000000)  # k_integrate_win: must not carry over
     a.integrate_frames(room_seq["depth"][:20], K[:20], T[:20], **kw)
+    assert _last_kernel_name(a) == "k_integrate_win<7>"
     ref = a.export()
     h = a.handle.value
     del a
     b = mqr_mod.VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=4096)
     assert b.handle.value == h and b.size() == 0  # the released grid, emptied
     b.integrate_frames(room_seq["depth"][:20], K[:20], T[:20], **kw)
+    assert _last_kernel_name(b).startswith("k_integrate_wt<7,")  # the default kernel again
     assert compare_volumes(b.export(), ref, 0.0) == 0.0
     c = mqr_mod.VoxelBlockGrid(voxel_size=0.01, block_resolution=16, block_count=4096)
     assert c.handle.value != h  # (b still alive: a new grid)

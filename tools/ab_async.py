@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
 """A/B of integrate variants in the bench's timed loop -- reset + integrate_frames over the 500-frame
 C2 walk, K steps back to back bracketed by synchronize -- in alternating rounds of one process, with
-every variant's volume compared to the first's bit for bit (blocks matched by key).  Default: the
-asynchronous return of mqr_integrate_frames on device frames (variant 0: the call returns with its last
-integrate queued) vs the synchronous one (variant bit 24: the streams drained before returning).
-Prints one JSON object (median ms per step per variant).
+every variant's volume compared to the first's bit for bit (blocks matched by key).  Default: MQR_DEVICE
+frames (the caller's stream waits for the call's last integrate) vs MQR_DEVICE_RESIDENT frames (it does
+not, so the next call's touch runs beside that integrate).  The synchronous return this tool first
+measured against is retired.  Prints one JSON object (median ms per step per variant).
 
-python tools/ab_async.py --rounds 7 --steps 100 [--variants 0,0x1000000,0x400000,r0]   (r: resident frames)
+python tools/ab_async.py --rounds 7 --steps 100 [--variants 0,r0,0x4000000]   (r: resident frames)
 """
 import argparse
 import json
@@ -24,7 +24,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--frames", type=int, default=500)
-    ap.add_argument("--variants", default="0,0x1000000")
+    ap.add_argument("--variants", default="0,r0")
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -36,7 +36,7 @@ def main():
     B, H, W = d.shape
     K, T = seq["K"].astype(np.float64), seq["T_wc"].astype(np.float64)
     torch.cuda.synchronize()
-    names = {0: "async", 0x1000000: "sync"}
+    names = {0: "device"}
     # a variant prefixed "r" passes the frames as MQR_DEVICE_RESIDENT (integrate_frames(resident=True))
     modes = {(("resident" if v == "r0" else v) if v.startswith("r") else names.get(int(v, 0), v)):
              int(v.lstrip("r"), 0) for v in a.variants.split(",")}

@@ -2,8 +2,8 @@
 """Interleaved A/B of integrate-kernel variants on the bench workload (one process, same data).
 
 python tools/ab_integrate.py --variants 0,4,0x4000000 --rounds 5
-(the kernels 0, 1, 2 and 4 and the configuration bits of mqr_vbg_set_variant, include/mqr.h; the rejected
-kernels this tool once compared are recorded in DESIGN.md section 4.1)
+(the kernels 0, 1, 2 and 4 and the path bits 12, 26 and 27 of mqr_vbg_set_variant, include/mqr.h; the rejected
+kernels and driver modes this tool once compared are recorded in DESIGN.md section 4.1)
 Prints per-variant median integrate-kernel ms per launch, touch ms, and step ms.
 """
 import argparse

@@ -25,7 +25,7 @@
 #   d2h         device -> host copy ceilings (tools/d2h_probe.py) with 1 / 4 / 8 staging threads
 #   chunkab     drop-in integrate() with 64- vs 127-frame hand-offs (tools/dropin_ab.py)
 #   conf        tools/conf_workload.py (the confidence kernel alone)
-#   abasync[:V] integrate_frames returning with its last integrate queued vs draining, or variants V (tools/ab_async.py)
+#   abasync[:V] integrate_frames on MQR_DEVICE vs MQR_DEVICE_RESIDENT frames, or variants V (tools/ab_async.py)
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
@@ -159,7 +159,7 @@ for step in ${STEPS:-tests}; do
       timeout -k 10 600 python -u tools/dropin_ab.py --profile --rounds 1 > gpurun_out/${TAG}_chunk_prof.json 2> gpurun_out/${TAG}_chunk_prof.txt || { tail -20 gpurun_out/${TAG}_chunk_prof.txt; exit 1; }
       grep -A22 "== CHUNK" gpurun_out/${TAG}_chunk_prof.txt | cut -c1-150 ;;
     abasync|abasync:*)
-      V=0,0x1000000; [ "$step" != abasync ] && V="${step#abasync:}"
+      V=0,r0; [ "$step" != abasync ] && V="${step#abasync:}"
       timeout -k 10 400 python -u tools/ab_async.py --rounds 7 --steps 100 --variants "$V" > gpurun_out/${TAG}_ab_async.json 2> gpurun_out/${TAG}_ab_async.err || { tail -20 gpurun_out/${TAG}_ab_async.err; exit 1; }
       cat gpurun_out/${TAG}_ab_async.json ;;
     conf)

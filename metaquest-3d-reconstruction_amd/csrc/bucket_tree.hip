@@ -8,6 +8,7 @@
 
 #include "bucket_tree.hpp"
 #include "device_block.hpp"
+#include "device_cub.hpp"
 
 namespace mqr {
 
@@ -74,15 +75,30 @@ __global__ void k_cm_level(int64_t first, int64_t count, float4* __restrict__ lo
     hi[n] = make_float4(fmaxf(hi[a].x, hi[b].x), fmaxf(hi[a].y, hi[b].y), fmaxf(hi[a].z, hi[b].z), 0.f);
 }
 
-static hipError_t sort_temp_bytes(int64_t n, hipStream_t s, size_t* bytes) {
-    return hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                              (const int32_t*)nullptr, (int32_t*)nullptr, (int)n, 0, 63, s);
-}
+// The build's scratch, stated once for bucket_tree_scratch_bytes and bucket_tree_build: the pieces, and the
+// sort (written once: its size query is part of the layout).  `ids` is read when the sort runs.
+struct BuildScratch {
+    uint64_t* keys;  // unsorted, then sorted
+    int32_t *sorted, *iota;
+    CubTemp tmp;
+    ScratchLayout L;
+    auto sort(const int32_t* const& ids, int64_t n, hipStream_t s) const {
+        return [this, &ids, n, s](void* t, size_t& b) {
+            return hipcub::DeviceRadixSort::SortPairs(t, b, (const uint64_t*)keys, keys + n, ids, sorted, (int)n, 0, 63, s);
+        };
+    }
+    hipError_t lay_out(const int32_t* const& ids, int64_t n, bool identity_ids, hipStream_t s) {
+        L.add(keys, 2 * n);
+        L.add(sorted, n);
+        L.add(iota, n, identity_ids);
+        return tmp.lay_out(L, sort(ids, n, s));
+    }
+};
 
 size_t bucket_tree_scratch_bytes(int64_t n, bool identity_ids, hipStream_t s) {
-    size_t tbs = 0;
-    if (sort_temp_bytes(n, s, &tbs) != hipSuccess) return 0;
-    return al256(sizeof(uint64_t) * 2 * n) + (identity_ids ? 2 : 1) * al256(sizeof(int32_t) * n) + al256(tbs + 16);
+    BuildScratch b;
+    const int32_t* ids = nullptr;
+    return b.lay_out(ids, n, identity_ids, s) == hipSuccess ? b.L.total() : 0;
 }
 
 void bucket_tree_enqueue_bounds(hipStream_t s, const float* V, const int32_t* ids, int64_t n, uint32_t* bb) {
@@ -96,20 +112,12 @@ void bucket_tree_enqueue_keys(hipStream_t s, const float* Q, const int32_t* ids,
 
 hipError_t bucket_tree_build(hipStream_t s, const float* V, const int32_t* ids, int64_t n, void* scratch,
                              size_t scratch_bytes, float4* lo, float4* hi, float4* pts, uint32_t* bb, BucketTree* out) {
-    size_t tbs = 0;
-    hipError_t err = sort_temp_bytes(n, s, &tbs);
+    BuildScratch b;
+    hipError_t err = b.lay_out(ids, n, !ids, s);
     if (err != hipSuccess) return err;
-    char* p = static_cast<char*>(scratch);
-    auto carve = [&](size_t bytes) {
-        char* r = p;
-        p += al256(bytes);
-        return r;
-    };
-    uint64_t* keys = reinterpret_cast<uint64_t*>(carve(sizeof(uint64_t) * 2 * n));  // unsorted, then sorted
-    int32_t* sorted = reinterpret_cast<int32_t*>(carve(sizeof(int32_t) * n));
-    int32_t* iota = ids ? nullptr : reinterpret_cast<int32_t*>(carve(sizeof(int32_t) * n));
-    void* tmp = carve(tbs + 16);
-    if (!scratch || (size_t)(p - static_cast<char*>(scratch)) > scratch_bytes) return hipErrorInvalidValue;
+    // the buffer is the caller's: the carve has to fit it
+    if (!scratch || !b.L.valid() || b.L.total() > scratch_bytes) return hipErrorInvalidValue;
+    b.L.bind(scratch);
 
     const int64_t P = bucket_tree_leaves(n);
     auto step = [&](hipError_t e) {
@@ -118,14 +126,14 @@ hipError_t bucket_tree_build(hipStream_t s, const float* V, const int32_t* ids, 
     const uint32_t init[6] = {~0u, ~0u, ~0u, 0u, 0u, 0u};
     step(hipMemcpyAsync(bb, init, sizeof init, hipMemcpyHostToDevice, s));
     if (!ids) {
-        hipLaunchKernelGGL(k_iota, dim3(nb(n)), dim3(256), 0, s, iota, n);
-        ids = iota;
+        hipLaunchKernelGGL(k_iota, dim3(nb(n)), dim3(256), 0, s, b.iota, n);
+        ids = b.iota;
     }
     bucket_tree_enqueue_bounds(s, V, ids, n, bb);
-    bucket_tree_enqueue_keys(s, V, ids, n, bb, keys);
+    bucket_tree_enqueue_keys(s, V, ids, n, bb, b.keys);
     step(hipGetLastError());
-    step(hipcub::DeviceRadixSort::SortPairs(tmp, tbs, (const uint64_t*)keys, keys + n, ids, sorted, (int)n, 0, 63, s));
-    hipLaunchKernelGGL(k_cm_leaf_boxes, dim3(nb(P)), dim3(256), 0, s, V, (const int32_t*)sorted, n, P, lo, hi, pts);
+    step(b.tmp.run(b.sort(ids, n, s)));
+    hipLaunchKernelGGL(k_cm_leaf_boxes, dim3(nb(P)), dim3(256), 0, s, V, (const int32_t*)b.sorted, n, P, lo, hi, pts);
     for (int64_t first = P / 2; first >= 1; first /= 2)
         hipLaunchKernelGGL(k_cm_level, dim3(nb(first)), dim3(256), 0, s, first, first, lo, hi);
     step(hipGetLastError());

@@ -29,6 +29,7 @@
 
 #include "mqr_common.hpp"
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "bucket_tree.hpp"
 #include "color_shared.hpp"
 
@@ -330,80 +331,82 @@ int cm_finish_colors(int device, hipStream_t s, const float* dV, int64_t nv, con
         set_error(std::string(who) + ": " + msg);
         rc = 1;
     };
-    size_t tb_sel = 0;
-    hipcub::CountingInputIterator<int32_t> it(0);
-    if (hipcub::DeviceSelect::Flagged(nullptr, tb_sel, it, (const uint8_t*)nullptr, (int32_t*)nullptr,
-                                      (int64_t*)nullptr, (int)nv, s) != hipSuccess) {
-        fail("select sizing failed");
-        return rc;
-    }
     // device staging from the device-block cache (device_block.hpp): the flags and index lists in one block,
     // the knn pass's (sized once the seen vertices are counted) in a second; both returned after the final
     // synchronisation
-    CachedBlock blk(device, (1 + 1 + 8) * (size_t)nv + 16 + tb_sel + 8 * 256);
+    ScratchLayout L;
+    uint8_t *fseen, *funseen;
+    int32_t* ids;  // seen, then unseen
+    int64_t* nsel;
+    L.add_each(nv, fseen, funseen);
+    L.add(ids, 2 * nv);
+    L.add(nsel, 2);
+    hipcub::CountingInputIterator<int32_t> it(0);
+    auto select_seen = [&](void* t, size_t& b) {
+        return hipcub::DeviceSelect::Flagged(t, b, it, fseen, ids, nsel, (int)nv, s);
+    };
+    auto select_unseen = [&](void* t, size_t& b) {
+        return hipcub::DeviceSelect::Flagged(t, b, it, funseen, ids + nv, nsel + 1, (int)nv, s);
+    };
+    CubTemp tmp;
+    if (tmp.lay_out(L, select_seen, select_unseen) != hipSuccess) {
+        fail("select sizing failed");
+        return rc;
+    }
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed(who, L.total());
     std::unique_ptr<CachedBlock> blk_knn;
-    CachedBlock* cur = &blk;
-    auto alloc = [&](size_t bytes) -> void* { return cur->take(std::max<size_t>(bytes, 16)); };
-    uint8_t* fseen = static_cast<uint8_t*>(alloc(nv));
-    uint8_t* funseen = static_cast<uint8_t*>(alloc(nv));
-    int32_t* ids = static_cast<int32_t*>(alloc(sizeof(int32_t) * 2 * nv));  // seen, then unseen
-    int64_t* nsel = static_cast<int64_t*>(alloc(2 * sizeof(int64_t)));
-    void* tmp = alloc(tb_sel);
-    if (!fseen || !funseen || !ids || !nsel || !tmp) fail("device allocation or upload failed");
     int64_t nseen = 0, nunseen = 0;
-    if (!rc) {
-        const unsigned gv = (unsigned)((nv + 255) / 256);
-        hipLaunchKernelGGL(k_cm_flags, dim3(gv), dim3(256), 0, s, cnt, nv, fseen, funseen);
-        size_t tb = tb_sel;
-        if (hipcub::DeviceSelect::Flagged(tmp, tb, it, fseen, ids, nsel, (int)nv, s) != hipSuccess ||
-            hipcub::DeviceSelect::Flagged(tmp, tb, it, funseen, ids + nv, nsel + 1, (int)nv, s) != hipSuccess)
-            fail("select failed");
-        int64_t h[2] = {0, 0};
-        if (!rc && (hipMemcpyAsync(h, nsel, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                    hipStreamSynchronize(s) != hipSuccess))
-            fail("visibility pass failed");
-        nseen = h[0];
-        nunseen = h[1];
-        if (!rc && hipMemsetAsync(dO, 0, sizeof(float) * 3 * nv, s) != hipSuccess) fail("memset failed");
-        if (!rc && nseen > 0)
-            hipLaunchKernelGGL(k_cm_out_seen, dim3(gv), dim3(256), 0, s, avg, cnt, nv, dO);
-        if (!rc && knn > 0 && nseen > 0 && nunseen > 0) {
-            // the tree's storage and its build scratch from a second block, sized by bucket_tree.hpp's rules
-            const size_t b_box = bucket_tree_node_bytes(nseen), b_scr = bucket_tree_scratch_bytes(nseen, false, s);
-            if (!b_scr) fail("knn allocation failed");
-            blk_knn.reset(new CachedBlock(device, 24 + 2 * b_box + 16 * (size_t)nseen + b_scr + 8 * 256));
-            cur = blk_knn.get();
-            uint32_t* bb = static_cast<uint32_t*>(alloc(6 * sizeof(uint32_t)));
-            float4* blo = static_cast<float4*>(alloc(b_box));
-            float4* bhi = static_cast<float4*>(alloc(b_box));
-            float4* pts = static_cast<float4*>(alloc(sizeof(float4) * nseen));
-            void* scratch = rc ? nullptr : alloc(b_scr);
-            if (!rc && (!bb || !blo || !bhi || !pts || !scratch)) fail("knn allocation failed");
-            BucketTree t{};
-            if (!rc && bucket_tree_build(s, dV, ids, nseen, scratch, b_scr, blo, bhi, pts, bb, &t) != hipSuccess)
-                fail("knn tree build failed");
-            // the wave's stack holds 64 entries and a nearest-first DFS at most depth + 2 (depth <= 27 for
-            // fewer than 2^31 points in buckets of 16)
-            if (!rc && t.depth + 2 > 64) fail("the knn tree is too deep for the traversal stack");
-            if (!rc) {
-                auto fill = [&](auto kern) {
-                    hipLaunchKernelGGL(kern, dim3(nb(nunseen)), dim3(256), sizeof(int32_t) * 4 * 64, s, dV, ids + nv, nunseen,
-                                       t.pts, t.n, t.P, t.lo, t.hi, avg, dO);
-                };
-                switch (knn) {  // knn in [1, 8] (checked on entry)
-                    case 1: fill(k_cm_knn_fill_wave<1>); break;
-                    case 2: fill(k_cm_knn_fill_wave<2>); break;
-                    case 3: fill(k_cm_knn_fill_wave<3>); break;
-                    case 4: fill(k_cm_knn_fill_wave<4>); break;
-                    case 5: fill(k_cm_knn_fill_wave<5>); break;
-                    case 6: fill(k_cm_knn_fill_wave<6>); break;
-                    case 7: fill(k_cm_knn_fill_wave<7>); break;
-                    default: fill(k_cm_knn_fill_wave<8>); break;
-                }
+    const unsigned gv = (unsigned)((nv + 255) / 256);
+    hipLaunchKernelGGL(k_cm_flags, dim3(gv), dim3(256), 0, s, cnt, nv, fseen, funseen);
+    if (tmp.run(select_seen) != hipSuccess || tmp.run(select_unseen) != hipSuccess) fail("select failed");
+    int64_t h[2] = {0, 0};
+    if (!rc && (hipMemcpyAsync(h, nsel, sizeof h, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess))
+        fail("visibility pass failed");
+    nseen = h[0];
+    nunseen = h[1];
+    if (!rc && hipMemsetAsync(dO, 0, sizeof(float) * 3 * nv, s) != hipSuccess) fail("memset failed");
+    if (!rc && nseen > 0)
+        hipLaunchKernelGGL(k_cm_out_seen, dim3(gv), dim3(256), 0, s, avg, cnt, nv, dO);
+    if (!rc && knn > 0 && nseen > 0 && nunseen > 0) {
+        // the tree's storage and its build scratch from a second block, sized by bucket_tree.hpp's rules
+        const size_t b_scr = bucket_tree_scratch_bytes(nseen, false, s);
+        ScratchLayout Lk;
+        uint32_t* bb;
+        float4 *blo, *bhi, *pts;
+        void* scratch;
+        Lk.add(bb, 6);
+        Lk.add_each(2 * bucket_tree_leaves(nseen), blo, bhi);
+        Lk.add(pts, nseen);
+        Lk.add_bytes(scratch, b_scr);
+        if (!b_scr) fail("knn allocation failed");
+        if (!rc) blk_knn.reset(new CachedBlock(device, Lk));
+        if (!rc && !blk_knn->p) rc = scratch_failed(who, Lk.total());
+        BucketTree t{};
+        if (!rc && bucket_tree_build(s, dV, ids, nseen, scratch, b_scr, blo, bhi, pts, bb, &t) != hipSuccess)
+            fail("knn tree build failed");
+        // the wave's stack holds 64 entries and a nearest-first DFS at most depth + 2 (depth <= 27 for
+        // fewer than 2^31 points in buckets of 16)
+        if (!rc && t.depth + 2 > 64) fail("the knn tree is too deep for the traversal stack");
+        if (!rc) {
+            auto fill = [&](auto kern) {
+                hipLaunchKernelGGL(kern, dim3(nb(nunseen)), dim3(256), sizeof(int32_t) * 4 * 64, s, dV, ids + nv, nunseen,
+                                   t.pts, t.n, t.P, t.lo, t.hi, avg, dO);
+            };
+            switch (knn) {  // knn in [1, 8] (checked on entry)
+                case 1: fill(k_cm_knn_fill_wave<1>); break;
+                case 2: fill(k_cm_knn_fill_wave<2>); break;
+                case 3: fill(k_cm_knn_fill_wave<3>); break;
+                case 4: fill(k_cm_knn_fill_wave<4>); break;
+                case 5: fill(k_cm_knn_fill_wave<5>); break;
+                case 6: fill(k_cm_knn_fill_wave<6>); break;
+                case 7: fill(k_cm_knn_fill_wave<7>); break;
+                default: fill(k_cm_knn_fill_wave<8>); break;
             }
         }
-        if (!rc && hipGetLastError() != hipSuccess) fail("kernel launch failed");
     }
+    if (!rc && hipGetLastError() != hipSuccess) fail("kernel launch failed");
     // the staging blocks go back to the cache at scope exit: everything queued on them has to be done
     if (hipStreamSynchronize(s) != hipSuccess && !rc) fail("kernel failed");
     return rc;
@@ -441,27 +444,28 @@ int mqr_color_vertices(int device, const float* vertices, int64_t nv, int vloc, 
     const int64_t HW = (int64_t)H * W;
     const bool hv = vloc != MQR_DEVICE, hi = img_loc != MQR_DEVICE, ho = out_loc != MQR_DEVICE;
     // device staging from the device-block cache (device_block.hpp), returned after the final synchronisation
-    CachedBlock blk(device, (hv ? 12 * (size_t)nv : 0) + (hi ? 7 * (size_t)HW * N : 0) +
-                                sizeof(ColorCam) * std::max(N, 1) + (ho ? 16 * (size_t)nv : 0) + 6 * 256);
-    auto dev = [&](const void* h, size_t bytes, bool host) -> const void* {
-        if (!host) return h;
-        void* p = blk.take(bytes);
-        if (!p || copy_to_device(device, p, h, bytes, s)) return nullptr;
-        return p;
-    };
-    const float* dV = static_cast<const float*>(dev(vertices, sizeof(float) * 3 * nv, vloc != MQR_DEVICE));
-    const uint8_t* dI = static_cast<const uint8_t*>(dev(images, (size_t)3 * HW * N, img_loc != MQR_DEVICE));
-    const float* dD = static_cast<const float*>(dev(depths, sizeof(float) * HW * N, img_loc != MQR_DEVICE));
-    const ColorCam* dC = static_cast<const ColorCam*>(dev(cams.data(), sizeof(ColorCam) * std::max(N, 1), true));
-    float* dO = colors_out;
-    int32_t* dN = counts_out;
-    if (out_loc != MQR_DEVICE) {
-        void* p = blk.take((sizeof(float) * 3 + sizeof(int32_t)) * nv);
-        dO = static_cast<float*>(p);
-        dN = p ? reinterpret_cast<int32_t*>(static_cast<float*>(p) + 3 * nv) : nullptr;
-    }
-    if (!dV || !dI || !dD || !dC || !dO) {
-        set_error("mqr_color_vertices: device allocation or upload failed");
+    ScratchLayout L;
+    float *d_v, *d_d, *d_o;
+    uint8_t* d_i;
+    ColorCam* dC;
+    int32_t* d_n;
+    L.add(d_v, 3 * nv, hv);
+    L.add(d_i, 3 * HW * N, hi);
+    L.add(d_d, HW * N, hi);
+    L.add(dC, N);
+    L.add(d_o, 3 * nv, ho);
+    L.add(d_n, nv, ho);
+    CachedBlock blk(device, L);
+    const float *dV = hv ? d_v : vertices, *dD = hi ? d_d : depths;
+    const uint8_t* dI = hi ? d_i : images;
+    float* dO = ho ? d_o : colors_out;
+    int32_t* dN = ho ? d_n : counts_out;
+    if (!blk.p) {
+        rc = scratch_failed("mqr_color_vertices", L.total());
+    } else if ((hv && copy_to_device(device, d_v, vertices, sizeof(float) * 3 * nv, s)) ||
+               (hi && (copy_to_device(device, d_i, images, (size_t)3 * HW * N, s) ||
+                       copy_to_device(device, d_d, depths, sizeof(float) * HW * N, s))) ||
+               copy_to_device(device, dC, cams.data(), sizeof(ColorCam) * N, s)) {
         rc = 1;
     } else {
         hipLaunchKernelGGL(k_color_vertices, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, s, dV, nv, dI, dD,
@@ -510,37 +514,38 @@ int mqr_color_map(int device, const float* vertices, int64_t nv, int vloc, const
     }
     // device staging from the device-block cache (device_block.hpp): the visibility pass's arrays in one
     // block (the fill's are cm_finish_colors' own), returned after the final synchronisation
-    const int64_t HW0 = (int64_t)H * W, NHW0 = HW0 * N;
-    const bool hv = vloc != MQR_DEVICE, hi = img_loc != MQR_DEVICE;
-    CachedBlock blk(device, (hv ? 12 * (size_t)nv : 0) + (hi ? 7 * (size_t)NHW0 : 0) + sizeof(ColorCam) * std::max(N, 1) +
-                                10 * (size_t)NHW0 + (24 + 4 + 12) * (size_t)nv + 16 * 256);
-    auto alloc = [&](size_t bytes) -> void* { return blk.take(std::max<size_t>(bytes, 16)); };
-    auto dev = [&](const void* h, size_t bytes, bool host) -> const void* {
-        if (!host) return h;
-        void* p = alloc(bytes);
-        if (!p || copy_to_device(device, p, h, bytes, s)) return nullptr;
-        return p;
-    };
+    const int64_t HW = (int64_t)H * W, NHW = HW * N;
+    const bool hv = vloc != MQR_DEVICE, hi = img_loc != MQR_DEVICE, ho = out_loc != MQR_DEVICE;
+    ScratchLayout L;
+    float *d_v, *d_t, *hx, *hy, *d_o;
+    uint8_t *d_i, *m0, *mask;
+    ColorCam* dC;
+    double* avg;
+    int32_t* cnt;
+    L.add(d_v, 3 * nv, hv);
+    L.add(d_i, 3 * NHW, hi);
+    L.add(d_t, NHW, hi);
+    L.add(dC, N);
+    L.add_each(NHW, hx, hy, m0, mask);
+    L.add(avg, 3 * nv);
+    L.add(cnt, nv);
+    L.add(d_o, 3 * nv, ho);
+    CachedBlock blk(device, L);
+    const float *dV = hv ? d_v : vertices, *dT = hi ? d_t : t_hit;
+    const uint8_t* dI = hi ? d_i : images;
+    float* dO = ho ? d_o : colors_out;
     int rc = 0;
     auto fail = [&](const char* msg) {
         set_error(msg);
         rc = 1;
     };
-    const int64_t HW = (int64_t)H * W, NHW = HW * N;
-    const float* dV = static_cast<const float*>(dev(vertices, sizeof(float) * 3 * nv, vloc != MQR_DEVICE));
-    const uint8_t* dI = static_cast<const uint8_t*>(dev(images, (size_t)3 * NHW, img_loc != MQR_DEVICE));
-    const float* dT = static_cast<const float*>(dev(t_hit, sizeof(float) * NHW, img_loc != MQR_DEVICE));
-    const ColorCam* dC = static_cast<const ColorCam*>(dev(cams.data(), sizeof(ColorCam) * std::max(N, 1), true));
-    float* hx = static_cast<float*>(alloc(sizeof(float) * NHW));
-    float* hy = static_cast<float*>(alloc(sizeof(float) * NHW));
-    uint8_t* m0 = static_cast<uint8_t*>(alloc(NHW));
-    uint8_t* mask = static_cast<uint8_t*>(alloc(NHW));
-    double* avg = static_cast<double*>(alloc(sizeof(double) * 3 * nv));
-    int32_t* cnt = static_cast<int32_t*>(alloc(sizeof(int32_t) * nv));
-    float* dO = out_loc == MQR_DEVICE ? colors_out : static_cast<float*>(alloc(sizeof(float) * 3 * nv));
-    if (!dV || !dI || !dT || !dC || !hx || !hy || !m0 || !mask || !avg || !cnt || !dO) {
-        fail("mqr_color_map: device allocation or upload failed");
-    }
+    if (!blk.p)
+        rc = scratch_failed("mqr_color_map", L.total());
+    else if ((hv && copy_to_device(device, d_v, vertices, sizeof(float) * 3 * nv, s)) ||
+             (hi && (copy_to_device(device, d_i, images, (size_t)3 * NHW, s) ||
+                     copy_to_device(device, d_t, t_hit, sizeof(float) * NHW, s))) ||
+             copy_to_device(device, dC, cams.data(), sizeof(ColorCam) * N, s))
+        rc = 1;
     if (!rc) {
         const unsigned gv = (unsigned)((nv + 255) / 256);
         cm_enqueue_masks(s, dT, NHW, H, W, (float)depth_trunc, disc_threshold, half_dilation, hx, hy, m0, mask);

@@ -215,25 +215,29 @@ int mqr_decode_color_frames(int device, const uint8_t* raw, int raw_loc, int N, 
     const bool stage_raw = raw_loc != MQR_DEVICE, stage_out = out_loc != MQR_DEVICE, stats = hist || lap_sums;
     const size_t in_bytes = (size_t)(N - 1) * (size_t)frame_stride + (size_t)L.valid_bytes;
     const size_t out_bytes = (size_t)N * H * W * 3;
-    const size_t b_raw = stage_raw ? al256(in_bytes) : 0, b_out = stage_out ? al256(out_bytes) : 0;
-    if (b_raw + b_out > c.scratch.cap) {
+    ScratchLayout scr, sts;
+    uint8_t *s_raw, *s_out;
+    uint32_t* d_hist;
+    unsigned long long* d_sums;
+    scr.add(s_raw, (int64_t)in_bytes, stage_raw);
+    scr.add(s_out, (int64_t)out_bytes, stage_out);
+    sts.add(d_hist, 256 * (int64_t)N, hist != nullptr);
+    sts.add(d_sums, 2 * (int64_t)N, lap_sums != nullptr);
+    MQR_REQUIRE(scr.valid() && sts.valid(), "bad frame shape");
+    if (scr.total() > c.scratch.cap) {
         MQR_CHECK_HIP(hipStreamSynchronize(c.s));
-        MQR_CHECK_HIP(c.scratch.reserve(b_raw + b_out, b_raw + b_out));
+        MQR_CHECK_HIP(c.scratch.reserve(scr.total(), scr.total()));
     }
-    const size_t b_hist = al256(sizeof(uint32_t) * 256 * N), b_sums = al256(sizeof(int64_t) * 2 * N);
-    if (stats && b_hist + b_sums > c.stats.cap) {
+    if (sts.total() > c.stats.cap) {
         MQR_CHECK_HIP(hipStreamSynchronize(c.s));
-        MQR_CHECK_HIP(c.stats.reserve(b_hist + b_sums, b_hist + b_sums));
+        MQR_CHECK_HIP(c.stats.reserve(sts.total(), sts.total()));
     }
+    scr.bind(c.scratch.p);
+    sts.bind(c.stats.p);
     if ((!stage_raw || !stage_out) && order_after_caller(device, c.s)) return 2;
-    char* sp = c.scratch.as<char>();
-    const uint8_t* d_raw = raw;
-    if (stage_raw) {
-        if (copy_to_device(device, sp, raw, in_bytes, c.s)) return 1;
-        d_raw = reinterpret_cast<const uint8_t*>(sp);
-        sp += b_raw;
-    }
-    uint8_t* d_out = stage_out ? reinterpret_cast<uint8_t*>(sp) : rgb_out;
+    const uint8_t* d_raw = stage_raw ? s_raw : raw;
+    if (stage_raw && copy_to_device(device, s_raw, raw, in_bytes, c.s)) return 1;
+    uint8_t* d_out = stage_out ? s_out : rgb_out;
 
     auto al4 = [](int64_t v) { return (v & 3) == 0; };
     const bool frames4 = N == 1 || al4(frame_stride);
@@ -261,10 +265,7 @@ int mqr_decode_color_frames(int device, const uint8_t* raw, int raw_loc, int N, 
     MQR_CHECK_HIP(hipGetLastError());
     MQR_CHECK_HIP(hipEventRecord(c.ev[1], c.s));
     if (stats) {
-        uint32_t* d_hist = hist ? c.stats.as<uint32_t>() : nullptr;
-        unsigned long long* d_sums =
-            lap_sums ? reinterpret_cast<unsigned long long*>(c.stats.as<char>() + b_hist) : nullptr;
-        MQR_CHECK_HIP(hipMemsetAsync(c.stats.p, 0, b_hist + b_sums, c.s));
+        MQR_CHECK_HIP(hipMemsetAsync(c.stats.p, 0, sts.total(), c.s));
         const int tiles = ((W + kTileW - 1) / kTileW) * ((H + kTileH - 1) / kTileH);
         const int per_frame = std::min({tiles, kStatsGroupsPerFrame, std::max(1, (kStatsGroups + N - 1) / N)});
         const dim3 sgrid((unsigned)per_frame, (unsigned)N);

@@ -25,6 +25,7 @@
 
 #include "mqr_common.hpp"
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "color_shared.hpp"
 #include "pair_reduce.hpp"
 
@@ -634,37 +635,30 @@ int mqr_colormap_create(int device, const float* vertices, int64_t nv, int vloc,
 
     // scratch of this call, from the device-block cache (returned after the final synchronisation)
     const int64_t nb = nvb * N + 1;
-    size_t tb1 = 0, tb2 = 0;
-    if (hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, (const int64_t*)nullptr, (int64_t*)nullptr, (int)nb, s) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, (const int64_t*)nullptr, (int64_t*)nullptr, (int)(nv + 1), s) != hipSuccess)
+    const bool hi = img_loc != MQR_DEVICE;
+    ScratchLayout L;
+    float *d_t, *hx, *hy;
+    uint8_t *m0, *mask;
+    int64_t *bcnt, *boff, *vcnt;
+    L.add(d_t, NHW, hi);
+    L.add_each(NHW, hx, hy, m0, mask);
+    L.add_each(nb, bcnt, boff);
+    L.add(vcnt, nv + 1);
+    auto scan_blocks = [&](void* t, size_t& b) { return hipcub::DeviceScan::ExclusiveSum(t, b, bcnt, boff, (int)nb, s); };
+    auto scan_vertices = [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::ExclusiveSum(t, b, vcnt, h->voff, (int)(nv + 1), s);
+    };
+    CubTemp tmp;
+    if (tmp.lay_out(L, scan_blocks, scan_vertices) != hipSuccess)
         return bail(1, "mqr_colormap_create: scan sizing failed");
-    const size_t tb = std::max(tb1, tb2);
-    CachedBlock blk(device, (img_loc != MQR_DEVICE ? 4 * (size_t)NHW : 0) + 10 * (size_t)NHW + 16 * (size_t)nb +
-                                8 * (size_t)(nv + 1) + tb + 16 * 256);
-    auto alloc = [&](size_t bytes) -> void* { return blk.take(std::max<size_t>(bytes, 16)); };
-    const float* dT = t_hit;
-    int rc = 0;
-    if (img_loc != MQR_DEVICE) {
-        void* p = alloc(sizeof(float) * NHW);
-        if (!p || copy_to_device(device, p, t_hit, sizeof(float) * NHW, s)) rc = 1;
-        dT = static_cast<const float*>(p);
-    }
-    float* hx = static_cast<float*>(alloc(sizeof(float) * NHW));
-    float* hy = static_cast<float*>(alloc(sizeof(float) * NHW));
-    uint8_t* m0 = static_cast<uint8_t*>(alloc(NHW));
-    uint8_t* mask = static_cast<uint8_t*>(alloc(NHW));
-    int64_t* bcnt = static_cast<int64_t*>(alloc(sizeof(int64_t) * nb));
-    int64_t* boff = static_cast<int64_t*>(alloc(sizeof(int64_t) * nb));
-    int64_t* vcnt = static_cast<int64_t*>(alloc(sizeof(int64_t) * (nv + 1)));
-    void* tmp = alloc(tb);
-    if (rc || !dT || !hx || !hy || !m0 || !mask || !bcnt || !boff || !vcnt || !tmp) {
-        (void)hipStreamSynchronize(s);
-        return bail(1, "mqr_colormap_create: device allocation or upload failed");
-    }
+    CachedBlock blk(device, L);
+    if (!blk.p) return bail(scratch_failed("mqr_colormap_create", L.total()), nullptr);
     auto fail = [&](const char* msg) {
         (void)hipStreamSynchronize(s);  // the scratch block goes back to the cache
         return bail(1, msg);
     };
+    const float* dT = hi ? d_t : t_hit;
+    if (hi && copy_to_device(device, d_t, t_hit, sizeof(float) * NHW, s)) return fail("mqr_colormap_create: upload failed");
     const unsigned gi = blocks_of(NHW), gv = (unsigned)nvb;
     const Params P = h->P;
     cm_enqueue_masks(s, dT, NHW, H, W, P.depth_trunc, disc_threshold, half_dilation, hx, hy, m0, mask);
@@ -674,9 +668,7 @@ int mqr_colormap_create(int device, const float* vertices, int64_t nv, int vloc,
         return fail("mqr_colormap_create: memset failed");
     hipLaunchKernelGGL(k_cmo_vis_block_count, dim3(gv, (unsigned)N), dim3(kThreads), 0, s, h->V, dT, mask, h->cams, P, bcnt);
     hipLaunchKernelGGL(k_cmo_vis_vertex_count, dim3(gv), dim3(kThreads), 0, s, h->V, dT, mask, h->cams, P, vcnt);
-    size_t t1 = tb, t2 = tb;
-    if (hipcub::DeviceScan::ExclusiveSum(tmp, t1, bcnt, boff, (int)nb, s) != hipSuccess ||
-        hipcub::DeviceScan::ExclusiveSum(tmp, t2, vcnt, h->voff, (int)(nv + 1), s) != hipSuccess)
+    if (tmp.run(scan_blocks) != hipSuccess || tmp.run(scan_vertices) != hipSuccess)
         return fail("mqr_colormap_create: scan failed");
     hipLaunchKernelGGL(k_cmo_kf_offsets, dim3((unsigned)((N + 1 + 255) / 256)), dim3(256), 0, s, boff, N, nvb, h->kf_off);
     hipLaunchKernelGGL(k_cmo_chunk_starts, dim3(1), dim3(1), 0, s, h->kf_off, N, h->chunk_start);
@@ -689,11 +681,16 @@ int mqr_colormap_create(int device, const float* vertices, int64_t nv, int vloc,
     h->n_chunks = 0;
     for (int c = 0; c < N; ++c) h->n_chunks += (h->h_kf_off[c + 1] - h->h_kf_off[c] + kThreads - 1) / kThreads;
     if (h->n_chunks >= (int64_t{1} << 31)) return fail("mqr_colormap_create: too many visibility pairs");
-    h->i2v = static_cast<int32_t*>(h->dmalloc(sizeof(int32_t) * std::max<int64_t>(h->pairs, 1)));
-    h->v2i = static_cast<int32_t*>(h->dmalloc(sizeof(int32_t) * std::max<int64_t>(h->pairs, 1)));
-    h->chunks = static_cast<Chunk*>(h->dmalloc(sizeof(Chunk) * std::max<int64_t>(h->n_chunks, 1)));
-    h->slabs = static_cast<double*>(h->dmalloc(sizeof(double) * kSums * std::max<int64_t>(h->n_chunks, 1)));
-    if (!h->i2v || !h->v2i || !h->chunks || !h->slabs) return fail("mqr_colormap_create: device allocation failed");
+    ScratchLayout Lh;  // the handle's arrays whose sizes the read-back gave: one allocation of the handle's
+    Lh.add_each(h->pairs, h->i2v, h->v2i);
+    Lh.add(h->chunks, h->n_chunks);
+    Lh.add(h->slabs, kSums * h->n_chunks);
+    void* held = Lh.valid() ? h->dmalloc(Lh.total()) : nullptr;
+    if (!held) {
+        (void)hipStreamSynchronize(s);
+        return bail(scratch_failed("mqr_colormap_create", Lh.total()), nullptr);
+    }
+    Lh.bind(held);
     if (h->pairs > 0) {
         hipLaunchKernelGGL(k_cmo_vis_block_emit, dim3(gv, (unsigned)N), dim3(kThreads), 0, s, h->V, dT, mask, h->cams, P,
                            boff, h->i2v);
@@ -875,11 +872,16 @@ int mqr_colormap_colors(mqr_colormap* h, int knn, float* colors, int32_t* counts
     MQR_CHECK_HIP(hipSetDevice(h->device));
     hipStream_t s = h->s;
     if (loc == MQR_DEVICE && order_after_caller(h->device, s)) return 2;
-    CachedBlock blk(h->device, (24 + 4 + 12) * (size_t)nv + 4 * 256);
-    double* avg = static_cast<double*>(blk.take(sizeof(double) * 3 * nv));
-    int32_t* cnt = static_cast<int32_t*>(blk.take(sizeof(int32_t) * nv));
-    float* dO = loc == MQR_DEVICE ? colors : static_cast<float*>(blk.take(sizeof(float) * 3 * nv));
-    MQR_REQUIRE(avg && cnt && dO, "mqr_colormap_colors: device allocation failed");
+    ScratchLayout L;
+    double* avg;
+    int32_t* cnt;
+    float* d_o;
+    L.add(avg, 3 * nv);
+    L.add(cnt, nv);
+    L.add(d_o, 3 * nv, loc != MQR_DEVICE);
+    CachedBlock blk(h->device, L);
+    if (!blk.p) return scratch_failed("mqr_colormap_colors", L.total());
+    float* dO = loc == MQR_DEVICE ? colors : d_o;
     int rc = 0;
     hipLaunchKernelGGL(k_cmo_color_avg, dim3(blocks_of(nv)), dim3(kThreads), 0, s, h->V, h->v2i, h->voff, h->cams,
                        h->images, h->P, avg, cnt);

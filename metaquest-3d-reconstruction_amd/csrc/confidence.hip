@@ -826,11 +826,6 @@ struct ConfCache {
 };
 ConfCache g_conf_cache[kMaxDevices];
 
-int scratch_failed(const char* who) {
-    (void)hipGetLastError();
-    set_error(std::string(who) + ": device allocation failed");
-    return 1;
-}
 }  // namespace
 
 #ifndef MQR_SRC_TAG
@@ -907,10 +902,11 @@ int mqr_confidence(int device, const float* depths, int depth_loc, int N, int H,
         dsrc = dd;
     }
     if (out_loc != MQR_DEVICE) {
-        const size_t bc = al256(sizeof(double) * nref * HW), bo = bc + sizeof(int32_t) * nref * HW;
-        MQR_REQUIRE(cc.d_out.reserve(bo, bo) == hipSuccess, "mqr_confidence: device allocation failed");
-        dconf = cc.d_out.as<double>();
-        dvalid = reinterpret_cast<int32_t*>(cc.d_out.as<char>() + bc);
+        ScratchLayout L;
+        L.add_each((int64_t)nref * HW, dconf, dvalid);
+        MQR_REQUIRE(L.valid() && cc.d_out.reserve(L.total(), L.total()) == hipSuccess,
+                    "mqr_confidence: device allocation failed");
+        L.bind(cc.d_out.p);
     }
     const dim3 grid((unsigned)((HW + 255) / 256), nref);
     const bool wide = frame_range > 31;    // a window of more than 64 frames: chunked defer masks
@@ -976,10 +972,13 @@ int mqr_check_div64(int device, int mode, uint64_t seed, uint64_t count, double 
     MQR_REQUIRE(mismatches && first_bad && (mode == 0 || mode == 1) && b_lo > 0 && b_hi >= b_lo, "bad arguments");
     MQR_CHECK_HIP(hipSetDevice(device));
     // scratch from the block cache: every return below releases it, after the null stream has drained
-    CachedBlock blk(device, 2 * 256);
-    unsigned long long* dm = (unsigned long long*)blk.take(sizeof(unsigned long long));
-    double* db = (double*)blk.take(2 * sizeof(double));
-    if (!dm || !db) return scratch_failed("mqr_check_div64");
+    ScratchLayout L;
+    unsigned long long* dm;
+    double* db;
+    L.add(dm, 1);
+    L.add(db, 2);
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("mqr_check_div64", L.total());
     StreamDrain drain{nullptr};
     MQR_CHECK_HIP(hipMemset(dm, 0, sizeof(unsigned long long)));
     MQR_CHECK_HIP(hipMemset(db, 0, 2 * sizeof(double)));
@@ -1007,11 +1006,13 @@ int mqr_pixel_error_map(int device, const float* ref_depth, const float* tgt_dep
     ConfFrame fr[2] = {};
     fill_frame(K_ref, T_cw_ref, nullptr, NAN, H, W, 0.f, fr[0]);
     fill_frame(K_tgt, T_cw_tgt, T_cw_inv_tgt, NAN, H, W, 0.f, fr[1]);
-    const size_t bm = sizeof(float) * HW;
-    CachedBlock blk(device, al256(sizeof(fr)) + 3 * al256(bm));
-    ConfFrame* dfr = (ConfFrame*)blk.take(sizeof(fr));
-    float *dr = (float*)blk.take(bm), *dt = (float*)blk.take(bm), *de = (float*)blk.take(bm);
-    if (!dfr || !dr || !dt || !de) return scratch_failed("mqr_pixel_error_map");
+    ScratchLayout L;
+    ConfFrame* dfr;
+    float *dr, *dt, *de;
+    L.add(dfr, 2);
+    L.add_each(HW, dr, dt, de);
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("mqr_pixel_error_map", L.total());
     StreamDrain drain{nullptr};
     MQR_CHECK_HIP(hipMemcpy(dfr, fr, sizeof(fr), hipMemcpyHostToDevice));
     MQR_CHECK_HIP(hipMemcpy(dr, ref_depth, sizeof(float) * HW, hipMemcpyHostToDevice));

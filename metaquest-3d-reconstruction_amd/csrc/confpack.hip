@@ -72,11 +72,14 @@ int mqr_confidence_counts(int device, const float* depths, int depth_loc, int N,
     if (!c.s) MQR_CHECK_HIP(hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking));
     if (!c.d_bad) MQR_CHECK_HIP(hipMalloc(&c.d_bad, sizeof(uint32_t)));
     if (!c.h_bad) MQR_CHECK_HIP(hipHostMalloc(&c.h_bad, sizeof(uint32_t), hipHostMallocDefault));
-    const size_t bc = mqr::al256(sizeof(double) * n), bm = bc + sizeof(int32_t) * n, bp = sizeof(uint16_t) * n;
-    MQR_CHECK_HIP(c.maps.reserve(bm, bm));
-    MQR_CHECK_HIP(c.packed.reserve(bp, bp));
-    double* dconf = c.maps.as<double>();
-    int32_t* dvalid = reinterpret_cast<int32_t*>(c.maps.as<char>() + bc);
+    mqr::ScratchLayout L;
+    double* dconf;
+    int32_t* dvalid;
+    L.add_each(n, dconf, dvalid);
+    MQR_REQUIRE(L.valid(), "bad shape");
+    MQR_CHECK_HIP(c.maps.reserve(L.total(), L.total()));
+    MQR_CHECK_HIP(c.packed.reserve(sizeof(uint16_t) * n, sizeof(uint16_t) * n));
+    L.bind(c.maps.p);
     uint16_t* dpacked = c.packed.as<uint16_t>();
     // the maps into HBM (mqr_confidence orders itself after the caller's stream and returns complete)
     if (int rc = mqr_confidence(device, depths, depth_loc, N, H, W, K, T_cw, T_cw_inv, frame_ok, ref_begin, ref_end,

@@ -1,9 +1,9 @@
 // device_block.hpp -- the library's device memory helpers (csrc/devmem.hip): per-call device staging from the
-// process's device-block cache (geom_block_alloc / geom_block_release): one block carved into 256-byte
-// aligned pieces and returned to the cache at scope exit, instead of a hipMalloc / hipFree pair per array
-// per call (hipFree synchronises the device; fresh allocations map pages).  The owner synchronises its
-// stream before the scope ends.  Also the grow-only buffer every module keeps between calls (GrowBuf), the
-// per-device stream table (StreamTable) and the carve of a geometry result (geom_alloc).
+// process's device-block cache (geom_block_alloc / geom_block_release): one block of a ScratchLayout's size
+// (scratch_layout.hpp), its pieces bound into it, returned to the cache at scope exit, instead of a hipMalloc /
+// hipFree pair per array per call (hipFree synchronises the device; fresh allocations map pages).  The owner
+// synchronises its stream before the scope ends.  Also the grow-only buffer every module keeps between calls
+// (GrowBuf), the per-device stream table (StreamTable) and the carve of a geometry result (geom_alloc).
 #pragma once
 
 #include <algorithm>
@@ -11,28 +11,24 @@
 #include <mutex>
 
 #include "mqr_common.hpp"
+#include "scratch_layout.hpp"
 
 namespace mqr {
 
 constexpr int kMaxDevices = 64;  // size of every per-device table (the index is checked against it)
 
-inline size_t al256(size_t x) { return (x + 255) & ~size_t(255); }
-
 struct CachedBlock {
     int device;
     void* p = nullptr;
-    size_t cap = 0, used = 0;
-    CachedBlock(int d, size_t bytes) : device(d) { p = geom_block_alloc(d, std::max<size_t>(bytes, 256), &cap); }
+    size_t cap = 0;
+    // p == nullptr when the layout is invalid or the device is out of memory: the one check of a call site
+    CachedBlock(int d, const ScratchLayout& L) : device(d) {
+        if (L.valid()) p = geom_block_alloc(d, std::max<size_t>(L.total(), 256), &cap);
+        if (p) L.bind(p);
+    }
     ~CachedBlock() { geom_block_release(device, p, cap); }
     CachedBlock(const CachedBlock&) = delete;
     CachedBlock& operator=(const CachedBlock&) = delete;
-    // the next piece of b bytes, or nullptr when the block is missing or full
-    void* take(size_t b) {
-        if (!p || used + al256(b) > cap) return nullptr;
-        char* r = static_cast<char*>(p) + used;
-        used += al256(b);
-        return r;
-    }
 };
 
 // The owner's side of that contract: declared after the block (so destroyed before it), it drains the stream
@@ -75,5 +71,9 @@ struct StreamTable {
 // One cached block for the positions, normals and triangles of a geometry result, recycled across results
 // (geom_block_alloc; mqr_geom_free returns it).  Non-zero with the error set when the device is out of memory.
 int geom_alloc(mqr_geom* g, int64_t nv, int64_t nt);
+
+// A scratch request that did not arrive: clears the sticky HIP error, sets "<who>: device allocation failed
+// (needed N bytes)", returns 1.
+int scratch_failed(const char* who, size_t bytes);
 
 }  // namespace mqr

@@ -32,6 +32,12 @@ hipError_t GrowBuf::reserve(size_t need, size_t alloc_bytes) {
     return hipSuccess;
 }
 
+int scratch_failed(const char* who, size_t bytes) {
+    (void)hipGetLastError();
+    set_error(std::string(who) + ": device allocation failed (needed " + std::to_string(bytes) + " bytes)");
+    return 1;
+}
+
 static std::mutex g_geom_mu;
 static std::vector<std::tuple<int, void*, size_t>> g_geom_cache;  // (device, block, capacity)
 constexpr size_t kGeomCacheBlocks = 4;

@@ -1241,7 +1241,7 @@ __global__ __launch_bounds__(kThreads) void k_points(const int32_t* __restrict__
 
 
 // ---------------------------------------------------------------- host side
-// Carve the grow-only per-volume scratch: nb[27n], 4 count/offset arrays of n, faces[3R^2 n], bits.
+// The grow-only per-volume scratch: nb[27n], 4 count/offset arrays of n, faces[3R^2 n], bits.
 struct ExScratch {
     int32_t *nb, *c0, *c1, *o0, *o1;
     uint32_t* faces;
@@ -1249,16 +1249,17 @@ struct ExScratch {
 };
 
 static int ex_scratch(mqr_vbg* v, int64_t n, bool mesh, ExScratch& e) {
-    const size_t sz_nb = al256(sizeof(int32_t) * 27 * n), sz_c = al256(sizeof(int32_t) * n);
+    const int64_t R2 = (int64_t)v->R * v->R;
+    ScratchLayout L;
+    L.add(e.nb, 27 * n);
+    L.add_each(n, e.c0, e.c1, e.o0, e.o1);
     // mesh: the byte-tile path's face tables (3 R^2 u32 per block), or the bit-row path's row records
     // (R^2 uint4), sign rows ((R + 2)^2 u32) and per-cube triangle counts (R^2 u64) per block,
     // whichever is larger
-    const size_t sz_f = mesh ? al256(std::max(sizeof(uint32_t) * 3 * v->R * v->R,
-                                              sizeof(uint32_t) * (6 * v->R * v->R + (v->R + 2) * (v->R + 2))) *
-                                     n)
-                             : 0;
-    const size_t sz_b = al256(sizeof(uint16_t) * 3 * v->R * v->R * n);
-    const size_t need = sz_nb + 4 * sz_c + sz_f + sz_b;
+    L.add(e.faces, std::max(3 * R2, 6 * R2 + (int64_t)(v->R + 2) * (v->R + 2)) * n, mesh);
+    L.add(e.bits, 3 * R2 * n);
+    MQR_REQUIRE(L.valid(), "extract: scratch size out of range");
+    const size_t need = L.total();
     if (v->ex_scratch_bytes < need) {
         MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
         GrowBuf b{v->ex_scratch, v->ex_scratch_bytes};  // the volume holds the pair as two plain fields
@@ -1269,17 +1270,7 @@ static int ex_scratch(mqr_vbg* v, int64_t n, bool mesh, ExScratch& e) {
     }
     // fine-grained (coherent) pinned memory: k_scan_counts writes the totals straight into it
     if (!v->h_ex) MQR_CHECK_HIP(hipHostMalloc(&v->h_ex, 4 * sizeof(int64_t), hipHostMallocCoherent));
-    char* p = static_cast<char*>(v->ex_scratch);
-    e.nb = reinterpret_cast<int32_t*>(p);
-    p += sz_nb;
-    e.c0 = reinterpret_cast<int32_t*>(p);
-    e.c1 = reinterpret_cast<int32_t*>(p + sz_c);
-    e.o0 = reinterpret_cast<int32_t*>(p + 2 * sz_c);
-    e.o1 = reinterpret_cast<int32_t*>(p + 3 * sz_c);
-    p += 4 * sz_c;
-    e.faces = reinterpret_cast<uint32_t*>(p);
-    p += sz_f;
-    e.bits = reinterpret_cast<uint16_t*>(p);
+    L.bind(v->ex_scratch);
     return 0;
 }
 

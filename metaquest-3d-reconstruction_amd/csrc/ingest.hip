@@ -194,11 +194,19 @@ static int decode_impl(int device, const float* raw, int raw_loc, int N, int H, 
     // scratch layout: [raw f32][conf f64][count i32] or [mask u8] [out f32], only the parts that are staged
     const bool stage_raw = raw_loc != MQR_DEVICE, stage_mask = any_mask && mask_loc != MQR_DEVICE,
                stage_out = out_loc != MQR_DEVICE;
-    const size_t b_raw = stage_raw ? al256(sizeof(float) * total) : 0;
-    const size_t b_conf = stage_mask && !mask8 ? al256(sizeof(double) * total) : 0;
-    const size_t b_vc = stage_mask ? al256((mask8 ? 1 : sizeof(int32_t)) * total) : 0;
-    const size_t b_out = stage_out ? al256(sizeof(float) * total) : 0;
-    if (decode_ctx_reserve(c, std::max<size_t>(b_raw + b_conf + b_vc + b_out, 256), N)) return 1;
+    ScratchLayout L;
+    float *s_raw, *s_out;
+    double* s_conf;
+    int32_t* s_vc;
+    uint8_t* s_m8;
+    L.add(s_raw, total, stage_raw);
+    L.add(s_conf, total, stage_mask && !mask8);
+    L.add(s_vc, total, stage_mask && !mask8);
+    L.add(s_m8, total, stage_mask && mask8);
+    L.add(s_out, total, stage_out);
+    MQR_REQUIRE(L.valid(), "bad frame shape");
+    if (decode_ctx_reserve(c, L.total(), N)) return 1;
+    L.bind(c.scratch.p);
     if ((!stage_raw || (any_mask && !stage_mask) || !stage_out) && order_after_caller(device, c.s)) return 2;
     for (int f = 0; f < N; ++f) {
         const double nr = nears[f], fa = fars[f];
@@ -214,29 +222,18 @@ static int decode_impl(int device, const float* raw, int raw_loc, int N, int H, 
         }
         d.mask = any_mask && has_mask[f];
     }
-    char* sp = c.scratch.as<char>();
-    const float* d_raw = raw;
-    if (stage_raw) {
-        if (copy_to_device(device, sp, raw, sizeof(float) * total, c.s)) return 1;
-        d_raw = reinterpret_cast<const float*>(sp);
-        sp += b_raw;
-    }
-    const double* d_conf = conf;
-    const int32_t* d_vc = valid_count;
-    const uint8_t* d_m8 = mask8;
+    const float* d_raw = stage_raw ? s_raw : raw;
+    const double* d_conf = stage_mask ? s_conf : conf;
+    const int32_t* d_vc = stage_mask ? s_vc : valid_count;
+    const uint8_t* d_m8 = stage_mask ? s_m8 : mask8;
+    if (stage_raw && copy_to_device(device, s_raw, raw, sizeof(float) * total, c.s)) return 1;
     if (stage_mask && mask8) {
-        if (copy_to_device(device, sp, mask8, total, c.s)) return 1;
-        d_m8 = reinterpret_cast<const uint8_t*>(sp);
-        sp += b_vc;
+        if (copy_to_device(device, s_m8, mask8, total, c.s)) return 1;
     } else if (stage_mask) {
-        if (copy_to_device(device, sp, conf, sizeof(double) * total, c.s)) return 1;
-        d_conf = reinterpret_cast<const double*>(sp);
-        sp += b_conf;
-        if (copy_to_device(device, sp, valid_count, sizeof(int32_t) * total, c.s)) return 1;
-        d_vc = reinterpret_cast<const int32_t*>(sp);
-        sp += b_vc;
+        if (copy_to_device(device, s_conf, conf, sizeof(double) * total, c.s)) return 1;
+        if (copy_to_device(device, s_vc, valid_count, sizeof(int32_t) * total, c.s)) return 1;
     }
-    float* d_out = stage_out ? reinterpret_cast<float*>(sp) : depth_out;
+    float* d_out = stage_out ? s_out : depth_out;
     DecodeFrame* d_fr = c.d_fr.as<DecodeFrame>();
     uint32_t* d_flags = c.d_flags.as<uint32_t>();
     MQR_CHECK_HIP(hipMemcpyAsync(d_fr, c.h_fr, sizeof(DecodeFrame) * N, hipMemcpyHostToDevice, c.s));

@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "mqr_common.hpp"
 
 // ------------------------------------------------------------------ RCCL, resolved at run time
@@ -500,58 +501,48 @@ static int device_plan(PlanScratch& S, hipStream_t st, const uint64_t* dkeys, in
     const int NC = 2 * W + 1;
     const int64_t nwg = (n + kPlanThreads - 1) / kPlanThreads;  // over union indices (U <= n)
     const int64_t nsend = n * (int64_t)std::min(W, 27);         // each union block goes to <= 27 ranks
-    size_t tb_sort = 0, tb_scan = 0, tb_wscan = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_sort, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                     (const int32_t*)nullptr, (int32_t*)nullptr, (int)n, 0, 64, st));
-    MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb_scan, (const int32_t*)nullptr, (int32_t*)nullptr,
-                                                   (int)n, st));
-    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb_wscan, (const int32_t*)nullptr, (int32_t*)nullptr,
-                                                   (int)(NC * nwg), st));
-    const size_t tb = std::max(tb_sort, std::max(tb_scan, tb_wscan));
-    // carve the scratch
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t o = off;
-        off += al256(bytes);
-        return o;
+    ScratchLayout L;
+    uint64_t *ks, *uni, *dm, *hm, *okeys;
+    int32_t *vi, *vs, *head, *incl, *first, *wcnt, *wbase, *send, *rdst, *rsrc;
+    PlanSummary* dsum;
+    L.add_each(n, ks, vi, vs, head, incl, uni, first, dm, hm);
+    L.add_each(NC * nwg, wcnt, wbase);
+    L.add(send, nsend);
+    L.add_each(n, rdst, rsrc, okeys);
+    L.add(dsum, 1);
+    auto sort_keys = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, dkeys, ks, vi, vs, (int)n, 0, 64, st);
     };
-    const size_t o_ks = take(8 * n), o_vi = take(4 * n), o_vs = take(4 * n), o_head = take(4 * n),
-                 o_incl = take(4 * n), o_uni = take(8 * n), o_first = take(4 * n), o_dm = take(8 * n),
-                 o_hm = take(8 * n), o_wcnt = take(4 * NC * nwg), o_wbase = take(4 * NC * nwg),
-                 o_send = take(4 * nsend), o_rdst = take(4 * n), o_rsrc = take(4 * n), o_okeys = take(8 * n),
-                 o_sum = take(sizeof(PlanSummary)), o_tmp = take(tb);
-    if (grow(S.buf, off)) return 1;
+    auto scan_heads = [&](void* t, size_t& b) { return hipcub::DeviceScan::InclusiveSum(t, b, head, incl, (int)n, st); };
+    auto scan_counts = [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::ExclusiveSum(t, b, wcnt, wbase, (int)(NC * nwg), st);
+    };
+    CubTemp tmp;
+    MQR_CHECK_HIP(tmp.lay_out(L, sort_keys, scan_heads, scan_counts));
+    MQR_REQUIRE(L.valid(), "merge plan: too many blocks");
+    if (grow(S.buf, L.total())) return 1;
+    L.bind(S.buf.p);
     if (!S.h_sum) MQR_CHECK_HIP(hipHostMalloc(&S.h_sum, sizeof(PlanSummary), hipHostMallocDefault));
-    char* b = S.buf.as<char>();
-    auto U64 = [&](size_t o) { return reinterpret_cast<uint64_t*>(b + o); };
-    auto I32 = [&](size_t o) { return reinterpret_cast<int32_t*>(b + o); };
-    PlanSummary* dsum = reinterpret_cast<PlanSummary*>(b + o_sum);
-    void* tmp = b + o_tmp;
     const unsigned g = (unsigned)((n + 255) / 256);
     MQR_CHECK_HIP(hipMemsetAsync(dsum, 0, sizeof(PlanSummary), st));
-    hipLaunchKernelGGL(k_plan_iota, dim3(g), dim3(256), 0, st, I32(o_vi), n);
-    size_t t = tb;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, t, dkeys, U64(o_ks), I32(o_vi), I32(o_vs), (int)n, 0, 64, st));
-    hipLaunchKernelGGL(k_plan_heads, dim3(g), dim3(256), 0, st, U64(o_ks), n, I32(o_head));
-    t = tb;
-    MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(tmp, t, I32(o_head), I32(o_incl), (int)n, st));
-    hipLaunchKernelGGL(k_plan_union, dim3(g), dim3(256), 0, st, U64(o_ks), I32(o_incl), n, U64(o_uni), I32(o_first),
-                       dsum);
-    hipLaunchKernelGGL(k_plan_masks, dim3((unsigned)nwg), dim3(kPlanThreads), 0, st, U64(o_uni), I32(o_first),
-                       U64(o_ks), I32(o_vs), n, mx, dsum, W, mode, root, me, U64(o_dm), U64(o_hm), I32(o_wcnt));
-    t = tb;
-    MQR_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, t, I32(o_wcnt), I32(o_wbase), (int)(NC * nwg), st));
-    hipLaunchKernelGGL(k_plan_lists, dim3((unsigned)nwg), dim3(kPlanThreads), 0, st, U64(o_uni), I32(o_first),
-                       I32(o_vs), mx, U64(o_dm), U64(o_hm), I32(o_wcnt), I32(o_wbase), dsum, W, mode, root, me,
-                       I32(o_send), I32(o_rdst), I32(o_rsrc), U64(o_okeys));
+    hipLaunchKernelGGL(k_plan_iota, dim3(g), dim3(256), 0, st, vi, n);
+    MQR_CHECK_HIP(tmp.run(sort_keys));
+    hipLaunchKernelGGL(k_plan_heads, dim3(g), dim3(256), 0, st, ks, n, head);
+    MQR_CHECK_HIP(tmp.run(scan_heads));
+    hipLaunchKernelGGL(k_plan_union, dim3(g), dim3(256), 0, st, ks, incl, n, uni, first, dsum);
+    hipLaunchKernelGGL(k_plan_masks, dim3((unsigned)nwg), dim3(kPlanThreads), 0, st, uni, first, ks, vs, n, mx, dsum, W,
+                       mode, root, me, dm, hm, wcnt);
+    MQR_CHECK_HIP(tmp.run(scan_counts));
+    hipLaunchKernelGGL(k_plan_lists, dim3((unsigned)nwg), dim3(kPlanThreads), 0, st, uni, first, vs, mx, dm, hm, wcnt,
+                       wbase, dsum, W, mode, root, me, send, rdst, rsrc, okeys);
     MQR_CHECK_HIP(hipGetLastError());
     MQR_CHECK_HIP(hipMemcpyAsync(S.h_sum, dsum, sizeof(PlanSummary), hipMemcpyDeviceToHost, st));
     MQR_CHECK_HIP(hipStreamSynchronize(st));
     out.H = static_cast<const PlanSummary*>(S.h_sum);
-    out.send_idx = I32(o_send);
-    out.recv_dst = I32(o_rdst);
-    out.recv_src = I32(o_rsrc);
-    out.out_keys = U64(o_okeys);
+    out.send_idx = send;
+    out.recv_dst = rdst;
+    out.recv_src = rsrc;
+    out.out_keys = okeys;
     return 0;
 }
 

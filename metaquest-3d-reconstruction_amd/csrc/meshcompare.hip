@@ -22,6 +22,7 @@
 
 #include "bucket_tree.hpp"
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "device_prims.hpp"
 #include "mesh_edges.hpp"
 #include "mqr_common.hpp"
@@ -211,12 +212,6 @@ __global__ void k_boundary_pairs(const int32_t* __restrict__ slots, int64_t nb, 
     pairs[2 * i + 1] = max(a, b);
 }
 
-static int alloc_failed(const char* who, size_t want) {
-    (void)hipGetLastError();
-    set_error(std::string(who) + ": device allocation failed (needed " + std::to_string(want) + " bytes)");
-    return 1;
-}
-
 }  // namespace mc
 }  // namespace mqr
 
@@ -239,14 +234,16 @@ int mqr_nn_create(int device, const float* targets, int64_t n, int loc, mqr_nn**
     const size_t b_scr = bucket_tree_scratch_bytes(n, true, s);
     MQR_REQUIRE(b_scr, "nn: the tree build's sort could not be sized");
     const bool host_in = loc == MQR_HOST;
-    const size_t b_pos = host_in ? sizeof(float) * 3 * n : 0;
-    const size_t want = al256(b_pos) + 256 + b_scr + 256;
-    CachedBlock blk(device, want);
-    if (!blk.p) return alloc_failed("nn", want);
-    float* d_pos = host_in ? (float*)blk.take(b_pos) : nullptr;
-    int32_t* flag = (int32_t*)blk.take(sizeof(int32_t));
-    void* scratch = blk.take(b_scr);
-    if (!flag || !scratch || (host_in && !d_pos)) return alloc_failed("nn", want);
+    const size_t b_pos = sizeof(float) * 3 * n;
+    ScratchLayout L;
+    float* d_pos;
+    int32_t* flag;
+    void* scratch;
+    L.add(d_pos, 3 * n, host_in);
+    L.add(flag, 1);
+    L.add_bytes(scratch, b_scr);
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("nn", L.total());
 
     const float* pos = targets;
     if (host_in) {
@@ -272,7 +269,7 @@ int mqr_nn_create(int device, const float* targets, int64_t n, int loc, mqr_nn**
     const size_t b_box = al256(bucket_tree_node_bytes(n)), b_pts = al256(sizeof(float4) * n);
     if (hipMalloc(&h->mem, 2 * b_box + b_pts + 256) != hipSuccess) {
         delete h;
-        return alloc_failed("nn", 2 * b_box + b_pts + 256);
+        return scratch_failed("nn", 2 * b_box + b_pts + 256);
     }
     char* base = (char*)h->mem;
     hipError_t e = bucket_tree_build(s, pos, nullptr, n, scratch, b_scr, (float4*)base, (float4*)(base + b_box),
@@ -310,28 +307,26 @@ int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* d
     const size_t lds = sizeof(int32_t) * 256 * (size_t)(h->t.depth + 2);
     MQR_REQUIRE(lds <= 64 * 1024, "nn: the tree is too deep for the traversal stack");
 
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                     (const int32_t*)nullptr, (int32_t*)nullptr, (int)nq, 0, 63, s));
     const bool host_in = loc == MQR_HOST, host_out = out_loc == MQR_HOST;
-    const size_t b_q = host_in ? sizeof(float) * 3 * nq : 0;
-    const size_t b_d = host_out ? sizeof(double) * nq : 0, b_i = host_out && idx ? sizeof(int32_t) * nq : 0;
-    const size_t want = al256(b_q) + al256(b_d) + al256(b_i) + 256 + 2 * al256(sizeof(uint64_t) * nq) +
-                        2 * al256(sizeof(int32_t) * nq) + al256(tb + 16) + 256;
-    CachedBlock blk(device, want);
-    if (!blk.p) return alloc_failed("nn", want);
-    float* d_q = host_in ? (float*)blk.take(b_q) : nullptr;
-    double* d_d = host_out ? (double*)blk.take(b_d) : nullptr;
-    int32_t* d_i = host_out && idx ? (int32_t*)blk.take(b_i) : nullptr;
-    int32_t* flag = (int32_t*)blk.take(sizeof(int32_t));
-    uint64_t* keys = (uint64_t*)blk.take(sizeof(uint64_t) * nq);
-    uint64_t* keys_s = (uint64_t*)blk.take(sizeof(uint64_t) * nq);
-    int32_t* ids = (int32_t*)blk.take(sizeof(int32_t) * nq);
-    int32_t* order = (int32_t*)blk.take(sizeof(int32_t) * nq);
-    void* tmp = blk.take(tb + 16);
-    if (!flag || !keys || !keys_s || !ids || !order || !tmp || (host_in && !d_q) ||
-        (host_out && (!d_d || (idx && !d_i))))
-        return alloc_failed("nn", want);
+    const size_t b_q = sizeof(float) * 3 * nq, b_d = sizeof(double) * nq, b_i = sizeof(int32_t) * nq;
+    ScratchLayout L;
+    float* d_q;
+    double* d_d;
+    int32_t *d_i, *flag, *ids, *order;
+    uint64_t *keys, *keys_s;
+    L.add(d_q, 3 * nq, host_in);
+    L.add(d_d, nq, host_out);
+    L.add(d_i, nq, host_out && idx);
+    L.add(flag, 1);
+    L.add_each(nq, keys, keys_s, ids, order);
+    auto sort_queries = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, (const uint64_t*)keys, keys_s, (const int32_t*)ids, order,
+                                                  (int)nq, 0, 63, s);
+    };
+    CubTemp tmp;
+    MQR_CHECK_HIP(tmp.lay_out(L, sort_queries));
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("nn", L.total());
 
     const float* Q = queries;
     if (host_in) {
@@ -355,11 +350,7 @@ int mqr_nn_query(mqr_nn* h, const float* queries, int64_t nq, int loc, double* d
     hipLaunchKernelGGL(k_iota, dim3(gq), dim3(kT), 0, s, ids, nq);
     bucket_tree_enqueue_keys(s, Q, ids, nq, h->t.bb, keys);
     MQR_CHECK_HIP(hipGetLastError());
-    {
-        size_t t2 = tb;
-        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint64_t*)keys, keys_s, (const int32_t*)ids,
-                                                         order, (int)nq, 0, 63, s));
-    }
+    MQR_CHECK_HIP(tmp.run(sort_queries));
     double* o_d = host_out ? d_d : dist;
     int32_t* o_i = host_out ? d_i : idx;
     hipLaunchKernelGGL(k_nn1, dim3(gq), dim3(256), lds, s, Q, (const int32_t*)order, nq, h->t.pts, h->t.n, h->t.P,
@@ -383,24 +374,27 @@ int mqr_distance_stats(int device, const double* dist, int64_t n, int loc, doubl
     hipStream_t s = g_streams.get(device);
     MQR_REQUIRE(s, "distance stats: no stream for the device");
 
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n,
-                                                    0, 63, s));
     const bool host_in = loc == MQR_HOST;
-    const size_t b_x = host_in ? sizeof(double) * n : 0;
+    const size_t b_x = sizeof(double) * n;
     const int64_t nblk = nb(n, kTile);
-    const size_t want = al256(b_x) + al256(sizeof(StatsRes)) + al256(sizeof(uint64_t) * n) +
-                        al256(sizeof(double) * kSlab * nblk) + al256(tb + 16) + 256;
-    CachedBlock blk(device, want);
-    if (!blk.p) return alloc_failed("distance stats", want);
-    double* d_x = host_in ? (double*)blk.take(b_x) : nullptr;
-    StatsRes* res = (StatsRes*)blk.take(sizeof(StatsRes));
-    uint64_t* sorted = (uint64_t*)blk.take(sizeof(uint64_t) * n);
-    double* slabs = (double*)blk.take(sizeof(double) * kSlab * nblk);
-    void* tmp = blk.take(tb + 16);
-    if (!res || !sorted || !slabs || !tmp || (host_in && !d_x)) return alloc_failed("distance stats", want);
-
     const double* x = dist;
+    ScratchLayout L;
+    double *d_x, *slabs;
+    StatsRes* res;
+    uint64_t* sorted;
+    L.add(d_x, n, host_in);
+    L.add(res, 1);
+    L.add(sorted, n);
+    L.add(slabs, kSlab * nblk);
+    // non-negative doubles order as their bit patterns (the sign bit is clear: 63 key bits)
+    auto sort_values = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortKeys(t, b, (const uint64_t*)x, sorted, (int)n, 0, 63, s);
+    };
+    CubTemp tmp;
+    MQR_CHECK_HIP(tmp.lay_out(L, sort_values));
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("distance stats", L.total());
+
     if (host_in) {
         if (copy_to_device(device, d_x, dist, b_x, s)) return 1;
         x = d_x;
@@ -414,11 +408,7 @@ int mqr_distance_stats(int device, const double* dist, int64_t n, int loc, doubl
     hipLaunchKernelGGL(k_stats<1>, dim3((unsigned)nblk), dim3(kT), 0, s, x, n, threshold, (const double*)res->r0, slabs);
     hipLaunchKernelGGL(k_reduce_slabs<kNS>, dim3(1), dim3(kT), 0, s, slabs, nblk, res->r1);
     MQR_CHECK_HIP(hipGetLastError());
-    {
-        // non-negative doubles order as their bit patterns (the sign bit is clear: 63 key bits)
-        size_t t2 = tb;
-        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, t2, (const uint64_t*)x, sorted, (int)n, 0, 63, s));
-    }
+    MQR_CHECK_HIP(tmp.run(sort_values));
     hipLaunchKernelGGL(k_median, dim3(1), dim3(64), 0, s, (const uint64_t*)sorted, n, res);
     MQR_CHECK_HIP(hipGetLastError());
     StatsRes r;
@@ -452,38 +442,35 @@ int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_
     const int64_t m = 3 * nt;
     const int vbits = ceil_log2(nv + 1);
     const int64_t nblk_t = nb(nt, kTile);
-    size_t tb_e = 0, tb_sel = 0;
-    hipcub::CountingInputIterator<int32_t> it(0);
-    if (nt > 0) {
-        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_e, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                         (const int32_t*)nullptr, (int32_t*)nullptr, (int)m, 0,
-                                                         32 + vbits, s));
-        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb_sel, it, (const uint8_t*)nullptr, (int32_t*)nullptr,
-                                                    (int64_t*)nullptr, (int)m, s));
-    }
-    const size_t tb = std::max(tb_e, tb_sel) + 16;
     const bool host_in = loc == MQR_HOST;
-    const size_t b_pos = host_in ? sizeof(float) * 3 * nv : 0, b_tri = host_in ? sizeof(int32_t) * m : 0;
-    const int64_t me = std::max<int64_t>(m, 1);  // entries of each edge array (a point cloud still takes one)
-    const size_t want = al256(b_pos) + al256(b_tri) + al256(sizeof(MeasureCtrl)) + al256(sizeof(int32_t) * nv) +
-                        2 * al256(sizeof(uint64_t) * me) + 2 * al256(sizeof(int32_t) * me) + al256(me) +
-                        al256(sizeof(double) * kSlab * nblk_t) + al256(tb) + 256;
-    CachedBlock blk(device, want);
-    if (!blk.p) return alloc_failed("mesh measure", want);
-    float* d_pos = host_in ? (float*)blk.take(b_pos) : nullptr;
-    int32_t* d_tri = host_in && nt > 0 ? (int32_t*)blk.take(b_tri) : nullptr;
-    MeasureCtrl* ctrl = (MeasureCtrl*)blk.take(sizeof(MeasureCtrl));
-    int32_t* vid = (int32_t*)blk.take(sizeof(int32_t) * nv);
-    uint64_t* keys = (uint64_t*)blk.take(sizeof(uint64_t) * me);
-    uint64_t* keys_s = (uint64_t*)blk.take(sizeof(uint64_t) * me);
-    int32_t* slot = (int32_t*)blk.take(sizeof(int32_t) * me);
-    int32_t* slot_s = (int32_t*)blk.take(sizeof(int32_t) * me);
-    uint8_t* bflag = (uint8_t*)blk.take(me);
-    double* slabs = (double*)blk.take(sizeof(double) * kSlab * nblk_t);
-    void* tmp = blk.take(tb);
-    if (!ctrl || !vid || !keys || !keys_s || !slot || !slot_s || !bflag || !slabs || !tmp ||
-        (host_in && (!d_pos || (nt > 0 && !d_tri))))
-        return alloc_failed("mesh measure", want);
+    const size_t b_pos = sizeof(float) * 3 * nv, b_tri = sizeof(int32_t) * m;
+    ScratchLayout L;
+    float* d_pos;
+    int32_t *d_tri, *vid, *slot, *slot_s;
+    MeasureCtrl* ctrl;
+    uint64_t *keys, *keys_s;
+    uint8_t* bflag;
+    double* slabs;
+    L.add(d_pos, 3 * nv, host_in);
+    L.add(d_tri, m, host_in && nt > 0);
+    L.add(ctrl, 1);
+    L.add(vid, nv);
+    L.add(keys, m);  // (a point cloud's empty edge arrays still take a slot each)
+    L.add_each(m, keys_s, slot, slot_s, bflag);
+    L.add(slabs, kSlab * nblk_t);
+    hipcub::CountingInputIterator<int32_t> it(0);
+    auto sort_edges = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, (const uint64_t*)keys, keys_s, (const int32_t*)slot, slot_s,
+                                                  (int)m, 0, 32 + vbits, s);
+    };
+    // boundary slots ascending (the unsorted slot array is free again: the compacted list goes there)
+    auto select_boundary = [&](void* t, size_t& b) {
+        return hipcub::DeviceSelect::Flagged(t, b, it, (const uint8_t*)bflag, slot, &ctrl->nboundary, (int)m, s);
+    };
+    CubTemp tmp;
+    MQR_CHECK_HIP(nt > 0 ? tmp.lay_out(L, sort_edges, select_boundary) : tmp.lay_out(L));
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("mesh measure", L.total());
 
     const float* pos = vertices;
     const int32_t* tri = triangles;
@@ -530,20 +517,12 @@ int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_
     // ---- the edge runs: boundary slots, closed and oriented
     hipLaunchKernelGGL(k_edge_keys<false>, dim3(nb(m)), dim3(kT), 0, s, tri, nt, (uint64_t)0, keys, slot);
     MQR_CHECK_HIP(hipGetLastError());
-    {
-        size_t t2 = tb;
-        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint64_t*)keys, keys_s, (const int32_t*)slot,
-                                                         slot_s, (int)m, 0, 32 + vbits, s));
-    }
+    MQR_CHECK_HIP(tmp.run(sort_edges));
     MQR_CHECK_HIP(hipMemsetAsync(bflag, 0, m, s));
     hipLaunchKernelGGL(k_edge_runs, dim3(nb(m)), dim3(kT), 0, s, (const uint64_t*)keys_s, (const int32_t*)slot_s, m, tri,
                        bflag, ctrl);
     MQR_CHECK_HIP(hipGetLastError());
-    {
-        // boundary slots ascending (the unsorted slot array is free again: the compacted list goes there)
-        size_t t2 = tb;
-        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(tmp, t2, it, (const uint8_t*)bflag, slot, &ctrl->nboundary, (int)m, s));
-    }
+    MQR_CHECK_HIP(tmp.run(select_boundary));
     MQR_CHECK_HIP(hipMemcpyAsync(&hc, ctrl, sizeof hc, hipMemcpyDeviceToHost, s));
     MQR_CHECK_HIP(hipStreamSynchronize(s));
 
@@ -557,7 +536,7 @@ int mqr_mesh_measure(int device, const float* vertices, int64_t nv, const int32_
         e->n = hc.nboundary;
         if (hipMalloc((void**)&e->pairs, sizeof(int32_t) * 2 * e->n) != hipSuccess) {
             delete e;
-            return alloc_failed("mesh measure", sizeof(int32_t) * 2 * (size_t)hc.nboundary);
+            return scratch_failed("mesh measure", sizeof(int32_t) * 2 * (size_t)hc.nboundary);
         }
         hipLaunchKernelGGL(k_boundary_pairs, dim3(nb(e->n)), dim3(kT), 0, s, (const int32_t*)slot, e->n, tri, e->pairs);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {

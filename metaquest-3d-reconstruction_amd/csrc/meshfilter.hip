@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "mesh_edges.hpp"
 #include "mqr_common.hpp"
 
@@ -369,14 +370,15 @@ struct Ctx {
         return 1;                                                                \
     }
 
-// hipcub's two-phase call, run(temp, temp_bytes) being the hipcub function bound to its arguments: the size
-// query (temp == nullptr), temp storage from the arena, the run (`sync`: then a wait), the stream-ordered release.
+// hipcub's two-phase call (device_cub.hpp) with the temp storage from the arena: the size query, the run
+// (`sync`: then a wait), the stream-ordered release.
 template <class Run>
 static int cub_call(Ctx& c, bool sync, Run run) {
-    size_t tb = 0;
-    MQR_CHECK_HIP(run(nullptr, tb));
-    MF_ALLOC(tmp, char, (int64_t)tb + 16);
-    MQR_CHECK_HIP(run(tmp, tb));
+    CubTemp t;
+    MQR_CHECK_HIP(t.size(run));
+    MF_ALLOC(tmp, char, (int64_t)t.bytes);
+    t.p = tmp;
+    MQR_CHECK_HIP(t.run(run));
     if (sync) MQR_CHECK_HIP(hipStreamSynchronize(c.s));
     c.release(tmp);
     return 0;

@@ -20,6 +20,7 @@
 #include <string>
 
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "device_prims.hpp"
 #include "mesh_edges.hpp"
 #include "mqr_common.hpp"
@@ -348,53 +349,44 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
     const uint64_t none = (uint64_t)nv << 32 | (uint64_t)nv;
     const int64_t nblk_t = nb(nt, kTile), nblk_e = nb(m, kTile);
 
-    // sort scratch of the two radix sorts (size queries touch no memory)
-    size_t tb_c = 0, tb_e = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_c, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                     (const int32_t*)nullptr, (int32_t*)nullptr, (int)m, 0, vbits, s));
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb_e, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                     (const int32_t*)nullptr, (int32_t*)nullptr, (int)m, 0, 32 + vbits, s));
-    const size_t tb = std::max(tb_c, tb_e) + 16;
-
     const bool host_in = loc == MQR_HOST;
-    const size_t b_pos = host_in ? sizeof(float) * 3 * nv : 0, b_col = host_in && colors ? sizeof(float) * 3 * nv : 0;
-    const size_t b_tri = host_in ? sizeof(int32_t) * m : 0;
-    const size_t want = al256(b_pos) + al256(b_col) + al256(b_tri) + al256(sizeof(Ctrl)) + al256(sizeof(Res)) +
-                        al256(sizeof(double) * 3 * nt) + al256(sizeof(double) * 3 * nv) + al256(sizeof(int32_t) * nv) +
-                        2 * al256(sizeof(uint64_t) * m) + 2 * al256(sizeof(int32_t) * m) +
-                        al256(sizeof(double) * kSlab * nblk_e) + al256(tb) + 256;
-    CachedBlock blk(device, want);
-    if (!blk.p) {
-        (void)hipGetLastError();
-        set_error("mesh quality: device allocation failed (needed " + std::to_string(want) + " bytes)");
-        return 1;
-    }
-    float* d_pos = host_in ? (float*)blk.take(b_pos) : nullptr;
-    float* d_col = host_in && colors ? (float*)blk.take(b_col) : nullptr;
-    int32_t* d_tri = host_in ? (int32_t*)blk.take(b_tri) : nullptr;
-    Ctrl* ctrl = (Ctrl*)blk.take(sizeof(Ctrl));
-    Res* res = (Res*)blk.take(sizeof(Res));
-    double* tn = (double*)blk.take(sizeof(double) * 3 * nt);
-    double* vn = (double*)blk.take(sizeof(double) * 3 * nv);
-    int32_t* parent = (int32_t*)blk.take(sizeof(int32_t) * nv);
-    uint64_t* keys = (uint64_t*)blk.take(sizeof(uint64_t) * m);
-    uint64_t* keys_s = (uint64_t*)blk.take(sizeof(uint64_t) * m);
-    int32_t* slot = (int32_t*)blk.take(sizeof(int32_t) * m);
-    int32_t* slot_s = (int32_t*)blk.take(sizeof(int32_t) * m);
-    double* slabs = (double*)blk.take(sizeof(double) * kSlab * nblk_e);
-    void* tmp = blk.take(tb);
-    if (!ctrl || !res || !tn || !vn || !parent || !keys || !keys_s || !slot || !slot_s || !slabs || !tmp ||
-        (host_in && (!d_pos || !d_tri || (colors && !d_col)))) {
-        set_error("mesh quality: device allocation failed (needed " + std::to_string(want) + " bytes)");
-        return 1;
-    }
+    const size_t b_pos = sizeof(float) * 3 * nv, b_tri = sizeof(int32_t) * m;
+    ScratchLayout L;
+    float *d_pos, *d_col;
+    int32_t *d_tri, *parent, *slot, *slot_s;
+    Ctrl* ctrl;
+    Res* res;
+    double *tn, *vn, *slabs;
+    uint64_t *keys, *keys_s;
+    L.add(d_pos, 3 * nv, host_in);
+    L.add(d_col, 3 * nv, host_in && colors);
+    L.add(d_tri, m, host_in);
+    L.add_each(1, ctrl, res);
+    L.add(tn, 3 * nt);
+    L.add(vn, 3 * nv);
+    L.add(parent, nv);
+    L.add_each(m, keys, keys_s, slot, slot_s);
+    L.add(slabs, kSlab * nblk_e);
+    // the two radix sorts; the corner sort borrows the edge sort's buffers
+    auto sort_corners = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, (const uint32_t*)keys, (uint32_t*)keys_s, (const int32_t*)slot,
+                                                  slot_s, (int)m, 0, vbits, s);
+    };
+    auto sort_edges = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, (const uint64_t*)keys, keys_s, (const int32_t*)slot, slot_s,
+                                                  (int)m, 0, 32 + vbits, s);
+    };
+    CubTemp tmp;
+    MQR_CHECK_HIP(tmp.lay_out(L, sort_corners, sort_edges));
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("mesh quality", L.total());
 
     const float* pos = vertices;
     const float* col = colors;
     const int32_t* tri = triangles;
     if (host_in) {
         if (copy_to_device(device, d_pos, vertices, b_pos, s) || copy_to_device(device, d_tri, triangles, b_tri, s) ||
-            (colors && copy_to_device(device, d_col, colors, b_col, s)))
+            (colors && copy_to_device(device, d_col, colors, b_pos, s)))
             return 1;
         pos = d_pos, col = d_col, tri = d_tri;
     } else if (order_after_caller(device, s)) {
@@ -424,12 +416,10 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
     // ---- vertex normals: the corner sort borrows the edge sort's buffers
     {
         uint32_t* ck = (uint32_t*)keys;
-        uint32_t* ck_s = (uint32_t*)keys_s;
+        const uint32_t* ck_s = (const uint32_t*)keys_s;
         hipLaunchKernelGGL(k_corner_keys, dim3(nb(m)), dim3(kT), 0, s, tri, m, ck, slot);
         MQR_CHECK_HIP(hipGetLastError());
-        size_t t2 = tb;
-        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint32_t*)ck, ck_s, (const int32_t*)slot, slot_s,
-                                                         (int)m, 0, vbits, s));
+        MQR_CHECK_HIP(tmp.run(sort_corners));
         MQR_CHECK_HIP(hipMemsetAsync(vn, 0, sizeof(double) * 3 * nv, s));
         hipLaunchKernelGGL(k_vertex_normals, dim3(nb(m)), dim3(kT), 0, s, ck_s, slot_s, m, tn, vn);
         MQR_CHECK_HIP(hipGetLastError());
@@ -437,11 +427,7 @@ int mqr_mesh_quality(int device, const float* vertices, int64_t nv, const float*
     // ---- topology
     hipLaunchKernelGGL(k_edge_keys<true>, dim3(nb(m)), dim3(kT), 0, s, tri, nt, none, keys, slot);
     MQR_CHECK_HIP(hipGetLastError());
-    {
-        size_t t2 = tb;
-        MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, t2, (const uint64_t*)keys, keys_s, (const int32_t*)slot,
-                                                         slot_s, (int)m, 0, 32 + vbits, s));
-    }
+    MQR_CHECK_HIP(tmp.run(sort_edges));
     hipLaunchKernelGGL(k_iota, dim3(nb(nv)), dim3(kT), 0, s, parent, nv);
     hipLaunchKernelGGL(k_union_vertices, dim3(nb(m)), dim3(kT), 0, s, keys_s, m, none, parent);
     hipLaunchKernelGGL(k_count_roots, dim3(nb(nv)), dim3(kT), 0, s, parent, nv, ctrl);

@@ -23,6 +23,7 @@
 #include <string>
 
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "device_prims.hpp"
 #include "mqr_common.hpp"
 
@@ -182,12 +183,6 @@ __global__ void __launch_bounds__(kT) k_sample(const float* __restrict__ pos, co
     }
 }
 
-static int alloc_failed(size_t want) {
-    (void)hipGetLastError();
-    set_error("mesh sample: device allocation failed (needed " + std::to_string(want) + " bytes)");
-    return 1;
-}
-
 }  // namespace ms
 }  // namespace mqr
 
@@ -227,25 +222,33 @@ int mqr_mesh_sample_points(int device, const float* vertices, int64_t nv, const 
     const bool host_in = in_loc == MQR_HOST, host_out = out_loc == MQR_HOST;
     const bool in_nrm = out_normals && !use_triangle_normal;  // the only reader of the vertex normals
     const int64_t nseg = (nt + kSeg - 1) / kSeg;
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)nt, s));
     const size_t b_v = sizeof(float) * 3 * nv, b_t = sizeof(int32_t) * 3 * nt, b_o = sizeof(float) * 3 * n;
-    const size_t want = (host_in ? al256(b_v) * (1 + (in_nrm ? 1 : 0) + (out_colors ? 1 : 0)) + al256(b_t) : 0) +
-                        (host_out ? al256(b_o) * (1 + (out_normals ? 1 : 0) + (out_colors ? 1 : 0)) +
-                                        (out_triangle ? al256(sizeof(int32_t) * n) : 0)
-                                  : 0) +
-                        al256(sizeof(Ctrl)) + 2 * al256(sizeof(uint64_t) * nt) + al256(sizeof(uint64_t) * nseg) +
-                        al256(tb + 16) + 256;
-    CachedBlock blk(device, want);
-    if (!blk.p) return alloc_failed(want);
+    ScratchLayout L;
+    float *d_v, *d_n, *d_c, *h_pos, *h_nrm, *h_col;
+    int32_t *d_t, *h_tri;
+    Ctrl* ctrl;
+    uint64_t *w, *cum, *coarse;
+    L.add(d_v, 3 * nv, host_in);
+    L.add(d_t, 3 * nt, host_in);
+    L.add(d_n, 3 * nv, host_in && in_nrm);
+    L.add(d_c, 3 * nv, host_in && out_colors);
+    L.add(h_pos, 3 * n, host_out);
+    L.add(h_nrm, 3 * n, host_out && out_normals);
+    L.add(h_col, 3 * n, host_out && out_colors);
+    L.add(h_tri, n, host_out && out_triangle);
+    L.add(ctrl, 1);
+    L.add_each(nt, w, cum);
+    L.add(coarse, nseg);
+    auto scan_weights = [&](void* t, size_t& b) {
+        return hipcub::DeviceScan::InclusiveSum(t, b, (const uint64_t*)w, cum, (int)nt, s);
+    };
+    CubTemp tmp;
+    MQR_CHECK_HIP(tmp.lay_out(L, scan_weights));
+    CachedBlock blk(device, L);
+    if (!blk.p) return scratch_failed("mesh sample", L.total());
     const float *pos = vertices, *nrm = in_nrm ? normals : nullptr, *col = out_colors ? colors : nullptr;
     const int32_t* tri = triangles;
     if (host_in) {
-        float* d_v = (float*)blk.take(b_v);
-        int32_t* d_t = (int32_t*)blk.take(b_t);
-        float* d_n = in_nrm ? (float*)blk.take(b_v) : nullptr;
-        float* d_c = out_colors ? (float*)blk.take(b_v) : nullptr;
-        if (!d_v || !d_t || (in_nrm && !d_n) || (out_colors && !d_c)) return alloc_failed(want);
         if (copy_to_device(device, d_v, vertices, b_v, s) || copy_to_device(device, d_t, triangles, b_t, s) ||
             (d_n && copy_to_device(device, d_n, normals, b_v, s)) || (d_c && copy_to_device(device, d_c, colors, b_v, s)))
             return 1;
@@ -253,20 +256,7 @@ int mqr_mesh_sample_points(int device, const float* vertices, int64_t nv, const 
     }
     float *o_pos = out_positions, *o_nrm = out_normals, *o_col = out_colors;
     int32_t* o_tri = out_triangle;
-    if (host_out) {
-        o_pos = (float*)blk.take(b_o);
-        o_nrm = out_normals ? (float*)blk.take(b_o) : nullptr;
-        o_col = out_colors ? (float*)blk.take(b_o) : nullptr;
-        o_tri = out_triangle ? (int32_t*)blk.take(sizeof(int32_t) * n) : nullptr;
-        if (!o_pos || (out_normals && !o_nrm) || (out_colors && !o_col) || (out_triangle && !o_tri))
-            return alloc_failed(want);
-    }
-    Ctrl* ctrl = (Ctrl*)blk.take(sizeof(Ctrl));
-    uint64_t* w = (uint64_t*)blk.take(sizeof(uint64_t) * nt);
-    uint64_t* cum = (uint64_t*)blk.take(sizeof(uint64_t) * nt);
-    uint64_t* coarse = (uint64_t*)blk.take(sizeof(uint64_t) * nseg);
-    void* tmp = blk.take(tb + 16);
-    if (!ctrl || !w || !cum || !coarse || !tmp) return alloc_failed(want);
+    if (host_out) o_pos = h_pos, o_nrm = h_nrm, o_col = h_col, o_tri = h_tri;
     StreamDrain drain{s};
 
     // ---- checks: nothing gathers through an index before the flags are read
@@ -289,10 +279,7 @@ int mqr_mesh_sample_points(int device, const float* vertices, int64_t nv, const 
     hipLaunchKernelGGL(k_areas, dim3(gt), dim3(kT), 0, s, pos, tri, nt, area, ctrl);
     hipLaunchKernelGGL(k_weights, dim3(gt), dim3(kT), 0, s, (const double*)area, nt, (const Ctrl*)ctrl, w);
     MQR_CHECK_HIP(hipGetLastError());
-    {
-        size_t t2 = tb;
-        MQR_CHECK_HIP(hipcub::DeviceScan::InclusiveSum(tmp, t2, (const uint64_t*)w, cum, (int)nt, s));
-    }
+    MQR_CHECK_HIP(tmp.run(scan_weights));
     hipLaunchKernelGGL(k_coarse, dim3(nb(nseg)), dim3(kT), 0, s, (const uint64_t*)cum, nt, nseg, coarse);
     MQR_CHECK_HIP(hipGetLastError());
     MQR_CHECK_HIP(hipEventRecord(ctx.ev[2], s));

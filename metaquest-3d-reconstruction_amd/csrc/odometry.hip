@@ -165,10 +165,14 @@ extern "C" int mqr_odometry_information_pairs(int device, const float* depths, i
     Pair* d_pairs = static_cast<Pair*>(c.get(1, sizeof(Pair) * (size_t)n_pairs));
     double* d_slabs = static_cast<double*>(c.get(2, sizeof(double) * kInfoSums * (size_t)n_pairs * (size_t)nblk));
     const size_t info_bytes = sizeof(double) * 36 * (size_t)n_pairs;
-    char* d_out = static_cast<char*>(c.get(3, info_bytes + sizeof(int64_t) * (size_t)n_pairs));
+    ScratchLayout L;  // the outputs
+    double* d_info;
+    int64_t* d_counts;
+    L.add(d_info, 36 * (int64_t)n_pairs);
+    L.add(d_counts, n_pairs);
+    void* d_out = c.get(3, L.total());
     MQR_REQUIRE(d_pairs && d_slabs && d_out, "odometry: device allocation failed");
-    double* d_info = reinterpret_cast<double*>(d_out);
-    int64_t* d_counts = reinterpret_cast<int64_t*>(d_out + info_bytes);
+    L.bind(d_out);
     MQR_CHECK_HIP(hipMemcpyAsync(d_pairs, hp.data(), sizeof(Pair) * (size_t)n_pairs, hipMemcpyHostToDevice, s));
     Params P;
     P.fx = K[0], P.fy = K[4], P.cx = K[2], P.cy = K[5];

@@ -24,6 +24,7 @@
 
 #include "mqr_common.hpp"
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "device_prims.hpp"
 
 struct mqr_scene {
@@ -403,64 +404,42 @@ static int build(mqr_scene* s) {
     MQR_REQUIRE(n > 0, "raycasting scene has no triangles");
     MQR_REQUIRE(n < (int64_t)1 << 30, "raycasting scene too large (>= 2^30 triangles)");
     hipStream_t st = s->stream;
-    int rc = 0;
     // Every temporary of the build carved from one block of the process's device-block cache
     // (geom_block_alloc), and the scene's leaf / node arrays from another: a rebuild or the next scene's
     // build reuses them instead of 15 hipMalloc / hipFree pairs: 2.93 -> 1.01 ms per build of a 2.1 M-triangle
     // mesh, the kernels' own 1.06 ms (tools/bvh_build_probe.py, profiles/r05_bvh_build_probe.json).
     const int64_t m1 = std::max<int64_t>(n - 1, 1);
-    size_t sort_bytes = 0, depth_sort_bytes = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                                     (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 63, st));
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, depth_sort_bytes, (const uint32_t*)nullptr,
-                                                     (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                     (int)m1, 0, 8, st));
-    const size_t tmp_bytes = std::max(sort_bytes, depth_sort_bytes) + 16;
-    const size_t sizes[] = {al256(sizeof(BuildTri) * n), al256(4 * n), al256(4 * n), al256(4 * 6), al256(4 * n),
-                            al256(4 * n), al256(8 * n), al256(8 * n), al256(8 * m1), al256(8 * n),
-                            al256(4 * std::max<int64_t>(m1, 512)), al256(4), al256(tmp_bytes)};
-    size_t total = 0;
-    for (size_t z : sizes) total += z;
-    size_t blk_cap = 0;
-    void* blk = geom_block_alloc(s->device, total, &blk_cap);
-    MQR_REQUIRE(blk, "raycasting scene: device allocation failed");
-    char* q = static_cast<char*>(blk);
-    auto carve = [&](int i) {
-        char* r = q;
-        q += sizes[i];
-        return r;
+    ScratchLayout L;
+    BuildTri* tris;
+    uint32_t *prim, *gid, *cb, *idx, *idx_sorted;
+    uint64_t *keys, *keys_sorted;
+    int32_t *child, *parent;
+    int *arrivals, *bad;
+    L.add_each(n, tris, prim, gid);
+    L.add(cb, 6);
+    L.add_each(n, idx, idx_sorted, keys, keys_sorted);
+    L.add(child, 2 * m1);
+    L.add(parent, 2 * n);
+    L.add(arrivals, std::max<int64_t>(m1, 512));
+    L.add(bad, 1);
+    // the refit's arrays live in the two key arrays: 2 x uint32 per former 64-bit key slot
+    uint32_t *depth = nullptr, *depth_s = nullptr, *ids = nullptr, *ids_s = nullptr;
+    auto sort_keys = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, keys, keys_sorted, idx, idx_sorted, (int)n, 0, 63, st);
     };
-    BuildTri* tris = reinterpret_cast<BuildTri*>(carve(0));
-    uint32_t* prim = reinterpret_cast<uint32_t*>(carve(1));
-    uint32_t* gid = reinterpret_cast<uint32_t*>(carve(2));
-    uint32_t* cb = reinterpret_cast<uint32_t*>(carve(3));
-    uint32_t* idx = reinterpret_cast<uint32_t*>(carve(4));
-    uint32_t* idx_sorted = reinterpret_cast<uint32_t*>(carve(5));
-    uint64_t* keys = reinterpret_cast<uint64_t*>(carve(6));
-    uint64_t* keys_sorted = reinterpret_cast<uint64_t*>(carve(7));
-    int32_t* child = reinterpret_cast<int32_t*>(carve(8));
-    int32_t* parent = reinterpret_cast<int32_t*>(carve(9));
-    int* arrivals = reinterpret_cast<int*>(carve(10));
-    int* bad = reinterpret_cast<int*>(carve(11));
-    void* tmp = carve(12);
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(st);  // (the block goes back to the cache: no kernel of this build may still use it)
-        geom_block_release(s->device, blk, blk_cap);
+    auto sort_depths = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, depth, depth_s, ids, ids_s, (int)m1, 0, 8, st);
     };
-#define RC_HIP(expr)                                                           \
-    do {                                                                       \
-        hipError_t _e = (expr);                                                \
-        if (_e != hipSuccess) {                                                \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(_e));      \
-            cleanup();                                                         \
-            return 1;                                                          \
-        }                                                                      \
-    } while (0)
+    CubTemp tmp;
+    MQR_CHECK_HIP(tmp.lay_out(L, sort_keys, sort_depths));
+    CachedBlock blk(s->device, L);
+    if (!blk.p) return scratch_failed("raycasting scene", L.total());
+    StreamDrain drain{st};  // (the block goes back to the cache: no kernel of this build may still use it)
     const uint32_t init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    RC_HIP(hipMemcpyAsync(cb, init, sizeof(init), hipMemcpyHostToDevice, st));
-    RC_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
-    RC_HIP(hipMemsetAsync(arrivals, 0, sizeof(int) * std::max<int64_t>(n - 1, 1), st));
-    RC_HIP(hipMemsetAsync(parent, 0xff, sizeof(int32_t) * 2 * n, st));
+    MQR_CHECK_HIP(hipMemcpyAsync(cb, init, sizeof(init), hipMemcpyHostToDevice, st));
+    MQR_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int), st));
+    MQR_CHECK_HIP(hipMemsetAsync(arrivals, 0, sizeof(int) * std::max<int64_t>(n - 1, 1), st));
+    MQR_CHECK_HIP(hipMemsetAsync(parent, 0xff, sizeof(int32_t) * 2 * n, st));
     int64_t base = 0;
     for (size_t g = 0; g < s->geoms.size(); ++g) {
         const auto& G = s->geoms[g];
@@ -468,56 +447,51 @@ static int build(mqr_scene* s) {
         hipLaunchKernelGGL(k_gather_tris, dim3((unsigned)std::min<int64_t>((G.nt + 255) / 256, kGatherGrid)), dim3(256), 0,
                            st, G.v, G.t, G.nt,
                            G.nv, base, (uint32_t)g, tris, prim, gid, cb, bad);
-        RC_HIP(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         base += G.nt;
     }
     const unsigned gb = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_morton, dim3(gb), dim3(256), 0, st, tris, n, cb, keys, idx);
-    RC_HIP(hipGetLastError());
-    size_t sb = sort_bytes;
-    RC_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sb, keys, keys_sorted, idx, idx_sorted, (int)n, 0, 63, st));
+    MQR_CHECK_HIP(hipGetLastError());
+    MQR_CHECK_HIP(tmp.run(sort_keys));
     {
-        const size_t sl = al256(sizeof(float4) * 3 * n);
-        s->bvh_blk = geom_block_alloc(s->device, sl + sizeof(float4) * 4 * m1, &s->bvh_cap);
-        if (!s->bvh_blk) {
-            set_error("raycasting scene: device allocation failed");
-            cleanup();
-            return 1;
-        }
-        s->leaf = static_cast<float4*>(s->bvh_blk);
-        s->node = reinterpret_cast<float4*>(static_cast<char*>(s->bvh_blk) + sl);
+        ScratchLayout Lb;  // what the scene keeps
+        Lb.add(s->leaf, 3 * n);
+        Lb.add(s->node, 4 * m1);
+        if (Lb.valid()) s->bvh_blk = geom_block_alloc(s->device, Lb.total(), &s->bvh_cap);
+        if (!s->bvh_blk) return scratch_failed("raycasting scene", Lb.total());
+        Lb.bind(s->bvh_blk);
     }
     if (n > 1) {
         hipLaunchKernelGGL(k_radix_tree, dim3((unsigned)((n - 1 + 255) / 256)), dim3(256), 0, st, keys_sorted, n,
                            child, parent);
-        RC_HIP(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(k_leaves, dim3(gb), dim3(256), 0, st, tris, prim, gid, idx_sorted, n, s->leaf);
-    RC_HIP(hipGetLastError());
+    MQR_CHECK_HIP(hipGetLastError());
     int h_bad = 0;
     if (n > 1) {
         // level-by-level refit: internal node depths -> sort ids by depth -> one launch per level
         const int64_t m = n - 1;
-        uint32_t* depth = reinterpret_cast<uint32_t*>(keys);  // 2 x uint32 per former 64-bit key slot
-        uint32_t* depth_s = depth + m;
-        uint32_t* ids = reinterpret_cast<uint32_t*>(keys_sorted);
-        uint32_t* ids_s = ids + m;
+        depth = reinterpret_cast<uint32_t*>(keys);
+        depth_s = depth + m;
+        ids = reinterpret_cast<uint32_t*>(keys_sorted);
+        ids_s = ids + m;
         int* lvl = arrivals;  // 512 ints: start[256], end[256] (arrivals has max(n - 1, 512) slots)
-        RC_HIP(hipMemsetAsync(lvl, 0, sizeof(int) * 512, st));
+        MQR_CHECK_HIP(hipMemsetAsync(lvl, 0, sizeof(int) * 512, st));
         const unsigned gm = (unsigned)((m + 255) / 256);
         hipLaunchKernelGGL(k_node_depth, dim3(gm), dim3(256), 0, st, parent, m, depth, ids, bad);
-        RC_HIP(hipGetLastError());
-        sb = depth_sort_bytes;
-        RC_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, sb, depth, depth_s, ids, ids_s, (int)m, 0, 8, st));
+        MQR_CHECK_HIP(hipGetLastError());
+        MQR_CHECK_HIP(tmp.run(sort_depths));  // (m == m1 here)
         hipLaunchKernelGGL(k_level_bounds, dim3(gm), dim3(256), 0, st, depth_s, m, lvl, lvl + 256);
-        RC_HIP(hipGetLastError());
+        MQR_CHECK_HIP(hipGetLastError());
         int h_lvl[512];
-        RC_HIP(hipMemcpyAsync(h_lvl, lvl, sizeof(h_lvl), hipMemcpyDeviceToHost, st));
-        RC_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-        RC_HIP(hipStreamSynchronize(st));
+        MQR_CHECK_HIP(hipMemcpyAsync(h_lvl, lvl, sizeof(h_lvl), hipMemcpyDeviceToHost, st));
+        MQR_CHECK_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+        MQR_CHECK_HIP(hipStreamSynchronize(st));
         if (h_bad & 2) {
             set_error("raycasting scene: BVH deeper than the traversal stack (96 levels)");
-            cleanup();
+            (void)hipStreamSynchronize(st);  // free_built releases bvh_blk, which queued kernels may still write
             free_built(s);
             return 1;
         }
@@ -526,21 +500,19 @@ static int build(mqr_scene* s) {
             if (cnt <= 0) continue;
             hipLaunchKernelGGL(k_refit_level, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, tris, idx_sorted,
                                child, ids_s + h_lvl[d], cnt, s->node);
-            RC_HIP(hipGetLastError());
+            MQR_CHECK_HIP(hipGetLastError());
         }
     }
-    RC_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
-    RC_HIP(hipStreamSynchronize(st));
-#undef RC_HIP
-    cleanup();
-    if (h_bad) {
+    MQR_CHECK_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, st));
+    MQR_CHECK_HIP(hipStreamSynchronize(st));
+    if (h_bad) {  // (the stream has just been drained)
         free_built(s);
         set_error("triangle index out of range of the vertex array");
         return 1;
     }
     s->ntri = n;
     s->built = true;
-    return rc;
+    return 0;
 }
 
 // CreateRaysPinhole's camera: invK = K^-1 in float64 (Eigen partial-pivot LU on the pinhole K,
@@ -659,24 +631,19 @@ int mqr_scene_cast_pinhole(mqr_scene* s, const double* K, const double* T_wc, in
     float *d_t = t_hit, *d_uv = uvs, *d_n = normals;
     uint32_t *d_g = geom_ids, *d_p = prim_ids;
     const bool host_out = out_loc != MQR_DEVICE;
-    const size_t per_px = host_out ? 4 + (geom_ids ? 4 : 0) + (prim_ids ? 4 : 0) + (uvs ? 8 : 0) +
-                                         (normals ? 12 : 0)
-                                   : 0;
-    CachedBlock blk(s->device, al256(sizeof(PinholeFrame) * n_frames) + per_px * total + 5 * 256);
-    bool ok = blk.p != nullptr;
-    PinholeFrame* d_fr = ok ? (PinholeFrame*)blk.take(sizeof(PinholeFrame) * n_frames) : nullptr;
-    if (ok && host_out) {
-        d_t = (float*)blk.take(sizeof(float) * total);
-        if (geom_ids) d_g = (uint32_t*)blk.take(sizeof(uint32_t) * total);
-        if (prim_ids) d_p = (uint32_t*)blk.take(sizeof(uint32_t) * total);
-        if (uvs) d_uv = (float*)blk.take(sizeof(float) * 2 * total);
-        if (normals) d_n = (float*)blk.take(sizeof(float) * 3 * total);
-    }
-    int rc = 0;
-    if (!ok) {
-        set_error("cast_pinhole: device allocation failed");
-        rc = 1;
-    }
+    ScratchLayout L;
+    PinholeFrame* d_fr;
+    float *h_t, *h_uv, *h_n;
+    uint32_t *h_g, *h_p;
+    L.add(d_fr, n_frames);
+    L.add(h_t, total, host_out);
+    L.add(h_g, total, host_out && geom_ids);
+    L.add(h_p, total, host_out && prim_ids);
+    L.add(h_uv, 2 * total, host_out && uvs);
+    L.add(h_n, 3 * total, host_out && normals);
+    CachedBlock blk(s->device, L);
+    if (host_out) d_t = h_t, d_g = h_g, d_p = h_p, d_uv = h_uv, d_n = h_n;
+    int rc = blk.p ? 0 : scratch_failed("cast_pinhole", L.total());
     if (!rc && hipMemcpyAsync(d_fr, hf.data(), sizeof(PinholeFrame) * n_frames, hipMemcpyHostToDevice, s->stream)) {
         set_error("cast_pinhole: upload failed");
         rc = 1;
@@ -720,28 +687,20 @@ int mqr_scene_cast_rays(mqr_scene* s, const float* rays, int64_t nrays, int rays
     float *d_t = t_hit, *d_uv = uvs, *d_n = normals;
     uint32_t *d_g = geom_ids, *d_p = prim_ids;
     const bool host_in = rays_loc != MQR_DEVICE, host_out = out_loc != MQR_DEVICE;
-    const size_t per_ray = (host_in ? 24 : 0) + (host_out ? 4 + (geom_ids ? 4 : 0) + (prim_ids ? 4 : 0) +
-                                                             (uvs ? 8 : 0) + (normals ? 12 : 0)
-                                                       : 0);
-    CachedBlock blk(s->device, per_ray * (size_t)nrays + 6 * 256);
-    bool ok = blk.p != nullptr;
-    if (ok && host_in) {
-        float* p = (float*)blk.take(sizeof(float) * 6 * nrays);
-        ok = copy_to_device(s->device, p, rays, sizeof(float) * 6 * nrays, s->stream) == 0;
-        d_r = p;
-    }
-    if (ok && host_out) {
-        d_t = (float*)blk.take(sizeof(float) * nrays);
-        if (geom_ids) d_g = (uint32_t*)blk.take(sizeof(uint32_t) * nrays);
-        if (prim_ids) d_p = (uint32_t*)blk.take(sizeof(uint32_t) * nrays);
-        if (uvs) d_uv = (float*)blk.take(sizeof(float) * 2 * nrays);
-        if (normals) d_n = (float*)blk.take(sizeof(float) * 3 * nrays);
-    }
-    int rc = 0;
-    if (!ok) {
-        set_error("cast_rays: device allocation / upload failed");
-        rc = 1;
-    }
+    ScratchLayout L;
+    float *h_r, *h_t, *h_uv, *h_n;
+    uint32_t *h_g, *h_p;
+    L.add(h_r, 6 * nrays, host_in);
+    L.add(h_t, nrays, host_out);
+    L.add(h_g, nrays, host_out && geom_ids);
+    L.add(h_p, nrays, host_out && prim_ids);
+    L.add(h_uv, 2 * nrays, host_out && uvs);
+    L.add(h_n, 3 * nrays, host_out && normals);
+    CachedBlock blk(s->device, L);
+    if (host_in) d_r = h_r;
+    if (host_out) d_t = h_t, d_g = h_g, d_p = h_p, d_uv = h_uv, d_n = h_n;
+    int rc = blk.p ? 0 : scratch_failed("cast_rays", L.total());
+    if (!rc && host_in) rc = copy_to_device(s->device, h_r, rays, sizeof(float) * 6 * nrays, s->stream);
     if (!rc) {
         hipLaunchKernelGGL(k_cast_rays, dim3((unsigned)((nrays + 255) / 256)), dim3(256), 0, s->stream, s->node,
                            s->leaf, s->ntri, d_r, nrays, d_t, d_g, d_p, d_uv, d_n);

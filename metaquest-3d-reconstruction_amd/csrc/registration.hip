@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "device_block.hpp"
+#include "device_cub.hpp"
 #include "device_prims.hpp"
 #include "mqr_common.hpp"
 #include "pair_reduce.hpp"
@@ -399,13 +400,17 @@ int sorted_keys(mqr_cloudset* cs, const float* pts, int64_t n, double e, uint64_
     MQR_CHECK_HIP(hipMemsetAsync(cs->d_flag, 0, sizeof(int), cs->s));
     hipLaunchKernelGGL(k_cell_keys, dim3(nb(n)), dim3(256), 0, cs->s, pts, n, e, keys.p, idx.p, cs->d_flag);
     MQR_CHECK_HIP(hipGetLastError());
-    size_t tb = 0;
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys.p, keys_s, idx.p, idx_s, (int)n, 0, 63, cs->s));
-    if (tmp.alloc((int64_t)tb + 16)) {
+    auto sort_cells = [&](void* t, size_t& b) {
+        return hipcub::DeviceRadixSort::SortPairs(t, b, keys.p, keys_s, idx.p, idx_s, (int)n, 0, 63, cs->s);
+    };
+    CubTemp ct;
+    MQR_CHECK_HIP(ct.size(sort_cells));
+    if (tmp.alloc((int64_t)ct.bytes)) {
         set_error("registration: device allocation failed");
         return 1;
     }
-    MQR_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys.p, keys_s, idx.p, idx_s, (int)n, 0, 63, cs->s));
+    ct.p = tmp.p;
+    MQR_CHECK_HIP(ct.run(sort_cells));
     int flag = 0;
     MQR_CHECK_HIP(hipMemcpyAsync(&flag, cs->d_flag, sizeof(int), hipMemcpyDeviceToHost, cs->s));
     MQR_CHECK_HIP(hipStreamSynchronize(cs->s));
@@ -453,13 +458,17 @@ int get_selection(mqr_cloudset* cs, int cloud, int kind, double param, const Sel
         hipLaunchKernelGGL(k_heads, dim3(nb(n)), dim3(256), 0, cs->s, keys_s.p, n, head.p);
         MQR_CHECK_HIP(hipGetLastError());
         hipcub::CountingInputIterator<int32_t> iota(0);
-        size_t tb = 0;
-        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(nullptr, tb, iota, head.p, start.p, d_num.p, (int)n, cs->s));
-        if (tmp.alloc((int64_t)tb + 16)) {
+        auto select_heads = [&](void* t, size_t& b) {
+            return hipcub::DeviceSelect::Flagged(t, b, iota, head.p, start.p, d_num.p, (int)n, cs->s);
+        };
+        CubTemp ct;
+        MQR_CHECK_HIP(ct.size(select_heads));
+        if (tmp.alloc((int64_t)ct.bytes)) {
             set_error("registration: device allocation failed");
             return 1;
         }
-        MQR_CHECK_HIP(hipcub::DeviceSelect::Flagged(tmp.p, tb, iota, head.p, start.p, d_num.p, (int)n, cs->s));
+        ct.p = tmp.p;
+        MQR_CHECK_HIP(ct.run(select_heads));
         int32_t m = 0;
         MQR_CHECK_HIP(hipMemcpyAsync(&m, d_num.p, sizeof(int32_t), hipMemcpyDeviceToHost, cs->s));
         MQR_CHECK_HIP(hipStreamSynchronize(cs->s));

@@ -108,17 +108,50 @@ def test_point_cloud_measure_and_errors():
     assert measure_mesh((v, t)).is_closed_oriented  # and the library is fine afterwards
 
 
+@pytest.mark.parametrize("nq", [1, 65])
+def test_nn_distances_do_not_depend_on_where_the_outputs_go(nq):
+    """mqr_nn_query stages its outputs only when they go to the host, and the index array only when asked for
+    (optional pieces of its scratch block): the distances are the same bits in all four cases, and so are the
+    indices where there are any."""
+    import ctypes
+    from mqr import _lib
+    from mqr._lib import MQR_DEVICE, MQR_HOST, call, ptr
+    from mqr.compare_mesh_to_ground_truth import NearestNeighbour
+    rng = np.random.default_rng(nq)
+    targets = rng.uniform(-1, 1, (300, 3)).astype(np.float32)
+    q = rng.uniform(-1.2, 1.2, (nq, 3)).astype(np.float32)
+    want = np.sqrt(((q[:, None, :].astype(np.float64) - targets[None].astype(np.float64)) ** 2).sum(-1)).min(1)
+    with NearestNeighbour(targets) as nn:
+        got = {}
+        for host_out in (True, False):
+            for with_idx in (False, True):
+                if host_out:
+                    d, i = np.empty(nq, np.float64), np.empty(nq, np.int32)
+                    call("mqr_nn_query", nn._h, ptr(q), nq, MQR_HOST, ptr(d), ptr(i) if with_idx else None, MQR_HOST)
+                else:
+                    bd, bi = _lib.DeviceBuffer(8 * nq), _lib.DeviceBuffer(4 * nq)
+                    call("mqr_nn_query", nn._h, ptr(q), nq, MQR_HOST, bd.ptr, bi.ptr if with_idx else None, MQR_DEVICE)
+                    d, i = bd.to_array((nq,), np.float64), bi.to_array((nq,), np.int32)
+                got[host_out, with_idx] = (d, i if with_idx else None)
+    first = got[True, True]
+    assert np.abs(first[0] - want).max() <= 1e-5  # float32-level agreement guards the setup (exactness: test_golden_cases)
+    for key, (d, i) in got.items():
+        assert np.array_equal(d.view(np.uint64), first[0].view(np.uint64)), key
+        if i is not None:
+            assert np.array_equal(i, first[1]), key
+
+
 CLOUD_SWEEP = """
 import numpy as np
 from mqr import _lib
 from mqr.compare_mesh_to_ground_truth import measure_mesh
 from mqr.geometry import DeviceArray, Tensor, TriangleMesh, device_mesh, mesh_fields
 p = np.random.default_rng(0).uniform(-1, 1, (262000, 3)).astype(np.float32)
-for nv in range(65300, 65500):  # host clouds: the request is 16 nv + about 2.5 KiB, 1 MiB near nv = 65376 to 65456
+for nv in range(65300, 65500):  # host clouds: al256(12 nv) + al256(4 nv) + 2 KiB (8 slots), 1 MiB at nv = 65408
     m = measure_mesh(p[:nv])
     assert m.num_vertices == nv and np.array_equal(m.max_bound, p[:nv].max(0))
 buf = _lib.DeviceBuffer.from_array(p)
-for nv in range(261400, 262000, 3):  # clouds in HBM: 4 nv + about 2.5 KiB, 1 MiB near nv = 261500 to 261824
+for nv in range(261400, 262000, 3):  # clouds in HBM: al256(4 nv) + 2 KiB, 1 MiB at nv = 261632
     mesh = TriangleMesh(Tensor(DeviceArray(buf, buf.ptr.value, (nv, 3), np.float32, 0)), np.zeros((nv, 3), np.float32),
                         Tensor(DeviceArray(buf, 0, (0, 3), np.int32, 0)), device="HIP:0")
     assert device_mesh(mesh_fields(mesh)) is not None  # measured in place

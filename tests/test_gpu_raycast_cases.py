@@ -202,3 +202,36 @@ def test_pinhole_equals_rays(generic, W, H, nf):
         _same_bits(one["t_hit"].numpy(), fused["t_hit"].numpy(), "single camera vs a stack of one")
     if (W, H) == (13, 11):
         assert np.isfinite(fused["t_hit"].numpy()).any() and np.isinf(fused["t_hit"].numpy()).any()
+
+
+def test_t_hit_does_not_depend_on_the_optional_outputs(generic):
+    """The ids, uvs and normals are optional outputs (four optional pieces of the casts' staging block when
+    the results go to the host): t_hit is the same bits with and without them, for both casts, with the
+    results left in HBM (the Python layer) and staged to host arrays (the C entry points)."""
+    from mqr import _lib
+    from mqr._lib import MQR_HOST, call, ptr
+    from mqr.raycasting import RaycastingScene
+    scene, _ = generic
+    s = _scene(scene)
+    W, H, nf = 7, 9, 3
+    K, T = _cameras(nf)
+    full = s.cast_pinhole(K, T, W, H, full=True)["t_hit"].numpy()
+    assert np.isfinite(full).any()
+    _same_bits(s.cast_pinhole(K, T, W, H, full=False)["t_hit"].numpy(), full, "cast_pinhole, full=False vs True")
+    rays = np.stack([RaycastingScene.create_rays_pinhole(K[f], T[f], W, H).numpy() for f in range(nf)])
+    _same_bits(s.cast_rays(rays, full=True)["t_hit"].numpy(), full, "cast_rays, full=True vs the pinhole cast")
+    _same_bits(s.cast_rays(rays, full=False)["t_hit"].numpy(), full, "cast_rays, full=False vs True")
+    # host outputs: t_hit alone, then with every optional output
+    n = nf * H * W
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    Kc, Tc = np.ascontiguousarray(K, np.float64), np.ascontiguousarray(T, np.float64)
+    for with_optional in (False, True):
+        opt = [np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty((n, 2), np.float32),
+               np.empty((n, 3), np.float32)] if with_optional else [None] * 4
+        po = [None if a is None else ptr(a) for a in opt]
+        t = np.empty(n, np.float32)
+        call("mqr_scene_cast_pinhole", s._h, ptr(Kc, _lib._f64p), ptr(Tc, _lib._f64p), nf, H, W, ptr(t), *po, MQR_HOST)
+        _same_bits(t.reshape(nf, H, W), full, f"cast_pinhole to the host, optional outputs {with_optional}")
+        t = np.empty(n, np.float32)
+        call("mqr_scene_cast_rays", s._h, ptr(r), n, MQR_HOST, ptr(t), *po, MQR_HOST)
+        _same_bits(t.reshape(nf, H, W), full, f"cast_rays to the host, optional outputs {with_optional}")

@@ -217,6 +217,11 @@ int mqr_geom_free(mqr_geom* g);
  * on a CUDA device stays there, and hand it to MQR_DEVICE inputs (mqr_scene_add_triangles,
  * mqr_mesh_filter_components, mqr_color_map) without a host round trip. */
 int mqr_geom_device_ptrs(mqr_geom* g, void** positions, void** normals, void** triangles);
+/* Vertex colours of a result (float32 [nv][3]).  Only mqr_mesh_simplify_clustering on a coloured input makes
+ * them: for every other producer device_colors reports a null pointer and copy_colors is status 2.
+ * device_colors: the array in place, as mqr_geom_device_ptrs.  copy_colors: nv*3 float32 into `loc` memory. */
+int mqr_geom_device_colors(mqr_geom* g, void** colors);
+int mqr_geom_copy_colors(mqr_geom* g, float* colors, int loc);
 
 /* build_confidence_map / compute_pixel_error_map
  * (confidence_estimation/estimate_depth_confidences.py:15-79, compute_pixel_error_map.py:120-220)
@@ -575,6 +580,45 @@ int mqr_mesh_sample_points(int device, const float* vertices, int64_t nv, const 
  * word, read once by each call). */
 int mqr_mesh_sample_last_ms(int device, float* call_ms, float* table_ms, float* sample_ms);
 int mqr_mesh_sample_set_flat_search(int flat);
+
+/* ---- mesh simplification by vertex clustering (scripts/downsample_fbx_mesh.py:129-283) ---------------
+ * mesh.simplify_vertex_clustering(voxel_size, Average) (csrc/meshsimplify.hip).  The rule is restated from
+ * Open3D's SimplifyVertexClustering as recalled (unpinned; where Open3D's result follows the
+ * iteration order of its hash containers the order is this package's own).  Quadric decimation is NOT here.
+ * vertices nv*3 float32, normals / colors nullable nv*3 float32, triangles nt*3 int32 (NULL with nt == 0), all
+ * in `loc` memory (MQR_DEVICE buffers are read in place).  All arithmetic is float64 on the widened values:
+ *   origin = (double)min_bound - voxel_size * 0.5 and cell(i) = floor(((double)p_i - origin) / voxel_size),
+ *   per axis; output vertex j is the j-th distinct cell in order of first appearance over i = 0 .. nv - 1 and
+ *   map[i] = j; its position is the members' sum in ascending input index (from +0), divided by (double)count
+ *   and rounded to float32; normals and colours likewise, neither renormalised nor clamped (without input
+ *   normals the result's normals are zeros; without input colours it has none).  Triangles in input order:
+ *   (a, b, c) = map[corners]; dropped when two are equal; rotated cyclically so the smallest index comes first
+ *   (the orientation stays); dropped when the same rotated triple occurred at a lower input index.  The same
+ *   cells in the opposite orientation are another triple: both stay.
+ * The result equals that rule bit for bit, whatever the residency, and a repeated call is identical.
+ * vertex_bounds: the exact bounds of the float32 coordinates as doubles (a -0 reads +0).
+ * mesh_cluster_count: the output vertex count of a voxel size (bounds, keys, one sort, segment heads; nothing
+ *   else is computed or written).
+ * mesh_simplify_clustering: the result is a device geometry from the block pool (mqr_geom_counts / _copy /
+ *   _device_ptrs / _device_colors / _copy_colors / _free).  stats[8]: input vertices, output vertices, input
+ *   triangles, triangles dropped as collapsed, triangles dropped as duplicates, output triangles, the largest
+ *   cell's population, the largest cell count along an axis.
+ * Errors (status 2; *out stays NULL): voxel_size not finite or <= 0, nv == 0, nv or nt >= 2^31, a non-finite
+ * coordinate, a triangle index outside [0, nv) (both found before any gather), and a grid of 2^21 or more
+ * cells along an axis ("the grid is too fine"; DEVIATION: Open3D's limit is INT_MAX cells -- the tighter one
+ * makes the cell key one 63-bit word).  The work runs on the calling thread's caller stream (mqr_set_stream)
+ * and is complete on return. */
+int mqr_vertex_bounds(int device, const float* vertices, int64_t nv, int loc, double* min3, double* max3);
+int mqr_mesh_cluster_count(int device, const float* vertices, int64_t nv, int loc, double voxel_size,
+                           int64_t* n_cells);
+int mqr_mesh_simplify_clustering(int device, const float* vertices, int64_t nv, const float* normals,
+                                 const float* colors, const int32_t* triangles, int64_t nt, int loc, double voxel_size,
+                                 mqr_geom** out, int64_t* stats);
+/* A measurement hook for tools/mesh_simplify_probe.py (as mqr_mesh_sample_last_ms): device time of the last
+ * completed mqr_mesh_simplify_clustering or mqr_mesh_cluster_count on `device`, ms, by events on the stream it
+ * ran on, from behind the input copies to the last kernel (the host's reads of the check flags and the cell
+ * count included): the whole call, the part up to the output vertices, and the triangles (0 for a count). */
+int mqr_mesh_simplify_last_ms(int device, float* call_ms, float* vertex_ms, float* triangle_ms);
 
 /* Fragment registration (refine_fragment_poses.py:122-271): a CLOUD SET of N float32 xyz clouds in
  * HBM and three batched operations over pairs of them, standing in for Open3D's

@@ -69,8 +69,9 @@ struct StreamTable {
 };
 
 // One cached block for the positions, normals and triangles of a geometry result, recycled across results
-// (geom_block_alloc; mqr_geom_free returns it).  Non-zero with the error set when the device is out of memory.
-int geom_alloc(mqr_geom* g, int64_t nv, int64_t nt);
+// (geom_block_alloc; mqr_geom_free returns it), with a colour array behind them when asked for.  Non-zero with
+// the error set when the device is out of memory.
+int geom_alloc(mqr_geom* g, int64_t nv, int64_t nt, bool colors = false);
 
 // A scratch request that did not arrive: clears the sticky HIP error, sets "<who>: device allocation failed
 // (needed N bytes)", returns 1.

@@ -78,15 +78,16 @@ void geom_block_release(int device, void* p, size_t cap) {
     (void)hipFree(p);
 }
 
-int geom_alloc(mqr_geom* g, int64_t nv, int64_t nt) {
+int geom_alloc(mqr_geom* g, int64_t nv, int64_t nt, bool colors) {
     const size_t sv = al256(sizeof(float) * 3 * std::max<int64_t>(nv, 1));
     const size_t st = al256(sizeof(int32_t) * 3 * std::max<int64_t>(nt, 1));
-    g->blk = geom_block_alloc(g->device, 2 * sv + st, &g->blk_cap);
+    g->blk = geom_block_alloc(g->device, (colors ? 3 : 2) * sv + st, &g->blk_cap);
     MQR_REQUIRE(g->blk, "geometry: device allocation failed");
     char* p = static_cast<char*>(g->blk);
     g->pos = reinterpret_cast<float*>(p);
     g->nrm = reinterpret_cast<float*>(p + sv);
     g->tri = reinterpret_cast<int32_t*>(p + 2 * sv);
+    g->col = colors ? reinterpret_cast<float*>(p + 2 * sv + st) : nullptr;
     return 0;
 }
 
@@ -273,6 +274,22 @@ int mqr_geom_device_ptrs(mqr_geom* g, void** positions, void** normals, void** t
     if (positions) *positions = g->nv ? g->pos : nullptr;
     if (normals) *normals = g->nv ? g->nrm : nullptr;
     if (triangles) *triangles = g->nt ? g->tri : nullptr;
+    return 0;
+}
+
+int mqr_geom_device_colors(mqr_geom* g, void** colors) {
+    MQR_REQUIRE(g && colors, "null argument");
+    *colors = g->nv ? g->col : nullptr;
+    return 0;
+}
+
+int mqr_geom_copy_colors(mqr_geom* g, float* colors, int loc) {
+    MQR_REQUIRE(g && colors, "null argument");
+    MQR_REQUIRE(g->col, "geometry: the result has no colours");
+    MQR_CHECK_HIP(hipSetDevice(g->device));
+    const hipMemcpyKind k = loc == MQR_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (loc == MQR_DEVICE && caller_stream()) MQR_CHECK_HIP(hipStreamSynchronize(caller_stream()));
+    if (g->nv && geom_copy_one(g->device, colors, g->col, sizeof(float) * 3 * g->nv, k)) return 1;
     return 0;
 }
 

@@ -242,7 +242,8 @@ struct mqr_geom {
     float* pos = nullptr;
     float* nrm = nullptr;
     int32_t* tri = nullptr;
-    void* blk = nullptr;  // when set, pos / nrm / tri are carved from this one allocation
+    float* col = nullptr;  // vertex colours (meshsimplify.hip); null for every other producer
+    void* blk = nullptr;  // when set, pos / nrm / tri (/ col) are carved from this one allocation
     size_t blk_cap = 0;   // its size (a recycled block may be larger than needed)
 };
 

@@ -90,6 +90,8 @@ SIGNATURES = {
     "mqr_geom_device_ptrs": (ctypes.c_int, [_vp, ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp)]),
     "mqr_geom_copy": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int]),
     "mqr_geom_free": (ctypes.c_int, [_vp]),
+    "mqr_geom_device_colors": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "mqr_geom_copy_colors": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     "mqr_confidence": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f32p,
                                       _f32p, _f32p, _u8p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                       ctypes.c_double, _vp, _vp, ctypes.c_int]),
@@ -156,6 +158,12 @@ SIGNATURES = {
                                               _vp, _vp, ctypes.c_int]),
     "mqr_mesh_sample_last_ms": (ctypes.c_int, [ctypes.c_int, _f32p, _f32p, _f32p]),
     "mqr_mesh_sample_set_flat_search": (ctypes.c_int, [ctypes.c_int]),
+    "mqr_mesh_simplify_last_ms": (ctypes.c_int, [ctypes.c_int, _f32p, _f32p, _f32p]),
+    "mqr_vertex_bounds": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, _f64p, _f64p]),
+    "mqr_mesh_cluster_count": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_double,
+                                              _i64p]),
+    "mqr_mesh_simplify_clustering": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64,
+                                                    ctypes.c_int, ctypes.c_double, ctypes.POINTER(_vp), _i64p]),
     "mqr_vbg_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_vbg_set_variant": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_check_div64": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
@@ -290,7 +298,8 @@ ORDERED = frozenset({
     "mqr_cloudset_create", "mqr_cloudset_voxel_down", "mqr_evaluate_pairs", "mqr_icp_pairs", "mqr_information_pairs",
     "mqr_odometry_information_pairs", "mqr_colormap_create", "mqr_colormap_colors",
     "mqr_nn_create", "mqr_nn_query", "mqr_distance_stats", "mqr_mesh_measure", "mqr_edge_list_copy",
-    "mqr_mesh_sample_points",
+    "mqr_mesh_sample_points", "mqr_geom_copy_colors", "mqr_vertex_bounds", "mqr_mesh_cluster_count",
+    "mqr_mesh_simplify_clustering",
 })
 _tls = threading.local()
 

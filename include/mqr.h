@@ -715,6 +715,30 @@ int mqr_colormap_optimize_ms(mqr_colormap* h, float* ms);
 int mqr_colormap_build_tag(char* buf, int n);
 int mqr_colormap_destroy(mqr_colormap* h);
 
+/* ---- volume ray casting (csrc/volumecast.hip) --------------------------------------
+ * Depth, vertex and normal maps of the fused surface for n pinhole cameras of one size, by marching each
+ * pixel's ray through the block hash (Open3D's VoxelBlockGrid::RayCast surface; the rule is restated from
+ * Open3D 0.19 as recalled and is not pinned against it).  K n*9 and T_wc n*16 (world -> camera) float64, host.
+ * block_keys (n_keys x 3 int32 by keys_loc, or NULL = every active block) are the blocks whose projections
+ * bound each ray's depth range; the march itself reads every block of the volume.  depth_min / depth_max clip
+ * the range in metres; depth is t * depth_scale; pixel_offset shifts the rays within their pixels (0: the
+ * pixel's corner, 0.5: its centre, the rays of mqr_scene_cast_pinhole).  flags: MQR_CAST_REFINE re-interpolates
+ * the crossing from two trilinear samples where all their corners are observed.  Outputs by out_loc, each may
+ * be NULL but not all: depth n*H*W, vertex and normal n*H*W*3 float32; a miss writes 0 everywhere, a normal
+ * whose stencil is not wholly observed is (0, 0, 0).  The call runs behind the volume's queued integrates and
+ * returns with its outputs complete.  n <= 0 or n > 65535 (a frame is one layer of the launch grid; cast more in
+ * several calls), H or W <= 0, range_map_down_factor <= 0, depth_min < 0,
+ * depth_max <= depth_min, a non-finite K / T_wc, fx or fy equal to 0, or all outputs NULL: status 2, nothing
+ * launched.  An empty volume renders all misses. */
+#define MQR_CAST_REFINE 1
+int mqr_vbg_ray_cast(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int keys_loc, const double* K,
+                     const double* T_wc, int n, int H, int W, float depth_scale, float depth_min, float depth_max,
+                     float weight_threshold, float trunc_voxel_multiplier, int range_map_down_factor,
+                     float pixel_offset, int flags, float* depth, float* vertex, float* normal, int out_loc);
+/* Device time (events on the volume's stream) of the last ray cast on the volume's device: the range map and
+ * the march, ms. */
+int mqr_vbg_ray_cast_last_ms(mqr_vbg* v, double* range_ms, double* march_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ SIGNATURES = {
                                               _i64p]),
     "mqr_mesh_simplify_clustering": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, _vp, ctypes.c_int64,
                                                     ctypes.c_int, ctypes.c_double, ctypes.POINTER(_vp), _i64p]),
+    "mqr_vbg_ray_cast": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _f64p, _f64p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                        _vp, _vp, _vp, ctypes.c_int]),
+    "mqr_vbg_ray_cast_last_ms": (ctypes.c_int, [_vp, _f64p, _f64p]),
     "mqr_vbg_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_vbg_set_variant": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_check_div64": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_double,
@@ -299,7 +304,7 @@ ORDERED = frozenset({
     "mqr_odometry_information_pairs", "mqr_colormap_create", "mqr_colormap_colors",
     "mqr_nn_create", "mqr_nn_query", "mqr_distance_stats", "mqr_mesh_measure", "mqr_edge_list_copy",
     "mqr_mesh_sample_points", "mqr_geom_copy_colors", "mqr_vertex_bounds", "mqr_mesh_cluster_count",
-    "mqr_mesh_simplify_clustering",
+    "mqr_mesh_simplify_clustering", "mqr_vbg_ray_cast",
 })
 _tls = threading.local()
 

@@ -589,12 +589,52 @@ class ReconstructionDataIO:
         self.save_colored_pcd_legacy(pcd)
 
 
+class RGBDPaths:
+    """Colour-aligned depth maps (config/project_path_config.py RGBDPathConfig):
+    ``<project>/<side>_color_aligned_depth/<timestamp>.npy``."""
+
+    COLOR_ALIGNED_DEPTH_DIR_MAP = {Side.LEFT: "left_color_aligned_depth", Side.RIGHT: "right_color_aligned_depth"}
+
+    def __init__(self, project_dir: Path):
+        self.project_dir = Path(project_dir)
+
+    def get_color_aligned_depth_filename(self, timestamp: int) -> str:
+        return f"{timestamp}.npy"
+
+    def get_color_aligned_depth_dir(self, side: Side) -> Path:
+        return self.project_dir / self.COLOR_ALIGNED_DEPTH_DIR_MAP[side]
+
+    def get_color_aligned_depth_path(self, side: Side, timestamp: int) -> Path:
+        return self.get_color_aligned_depth_dir(side) / self.get_color_aligned_depth_filename(timestamp)
+
+
+class RGBDDataIO:
+    """The reference's ``RGBDDataIO`` (scripts/dataio/rgbd_data_io.py): one ``np.save`` file per colour frame."""
+
+    def __init__(self, image_data_io, depth_data_io, rgbd_path_config: RGBDPaths):
+        self.image_data_io = image_data_io
+        self.depth_data_io = depth_data_io
+        self.rgbd_path_config = rgbd_path_config
+
+    def load_color_aligned_depth(self, side: Side, timestamp: int) -> np.ndarray:
+        path = self.rgbd_path_config.get_color_aligned_depth_path(side=side, timestamp=timestamp)
+        if not path.exists():
+            raise FileNotFoundError(f"Color-aligned depth file not found: {path}")
+        return np.load(path)
+
+    def save_color_aligned_depth(self, depth_map: np.ndarray, side: Side, timestamp: int):
+        path = self.rgbd_path_config.get_color_aligned_depth_path(side=side, timestamp=timestamp)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        np.save(path, depth_map)
+
+
 class DataIO:
-    """A capture directory: ``.depth`` (DepthDataIO), ``.color`` (ImageDataIO) and ``.reconstruction``
-    (ReconstructionDataIO, the results)."""
+    """A capture directory: ``.depth`` (DepthDataIO), ``.color`` (ImageDataIO), ``.rgbd`` (RGBDDataIO, the
+    colour-aligned depth maps) and ``.reconstruction`` (ReconstructionDataIO, the results)."""
 
     def __init__(self, project_dir: Path):
         self.project_dir = Path(project_dir).resolve()
         self.depth = DepthDataIO(self.project_dir)
         self.color = ImageDataIO(self.project_dir)
+        self.rgbd = RGBDDataIO(self.color, self.depth, RGBDPaths(self.project_dir))
         self.reconstruction = ReconstructionDataIO(self.project_dir)

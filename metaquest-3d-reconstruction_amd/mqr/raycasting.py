@@ -8,6 +8,9 @@ depth (reconstruct_scene.py:197-201; o3d_utils.py:324-341; optimize_color_pose.p
     rays = RaycastingScene.create_rays_pinhole(K, T_wc, width_px, height_px)
     depth = scene.cast_rays(rays)['t_hit'].cpu().numpy()
 
+``raycast_in_color_view`` also takes a ``VoxelBlockGrid`` (the volume marched directly, no mesh), and
+``render_color_aligned_depth`` drives either over a capture (reconstruct_scene.py:181-225).
+
 The BVH is built on the device (libmqr_hip.so, csrc/raycast.hip) at the first query after the
 geometry changed.  ``cast_pinhole`` is the fused path (rays generated on the device, identical
 to create_rays_pinhole + cast_rays).  t_hit is inf where a ray hits nothing; ids are
@@ -151,12 +154,20 @@ class RaycastingScene:
         return self._tensors([o for o in outs if o is not None], shape, full)
 
 
-def raycast_in_color_view(scene: RaycastingScene, dataset, batch: int = 16):
+def raycast_in_color_view(scene, dataset, batch: int = 16, **cast_kw):
     """Generator of colour-aligned depth maps, one (H, W) float32 per dataset frame in order
-    (reference o3d_utils.py:324-341); consecutive same-size frames are cast together."""
+    (reference o3d_utils.py:324-341); consecutive same-size frames are cast together.  `scene` is a
+    RaycastingScene (the mesh cast) or a VoxelBlockGrid: the volume itself is then marched
+    (``ray_cast_frames`` at the pixel centres, refined crossings, metric depth; `cast_kw` passes its
+    thresholds through) and its misses (0) become inf, the mesh cast's t_hit convention."""
     from .o3d_utils import compute_o3d_intrinsic_matrices
+    from .vbg import VoxelBlockGrid
     K = compute_o3d_intrinsic_matrices(dataset).astype(np.float32).astype(np.float64)
     T = dataset.transforms.extrinsics_wc.astype(np.float32).astype(np.float64)
+    volume = isinstance(scene, VoxelBlockGrid)
+    if cast_kw and not volume:
+        raise TypeError(f"raycast_in_color_view: {sorted(cast_kw)} are the volume cast's arguments; a "
+                        "RaycastingScene takes none")
     n = len(dataset)
     i = 0
     while i < n:
@@ -164,7 +175,54 @@ def raycast_in_color_view(scene: RaycastingScene, dataset, batch: int = 16):
         j = i + 1
         while j < n and j - i < batch and int(dataset.widths[j]) == w and int(dataset.heights[j]) == h:
             j += 1
-        depth = scene.cast_pinhole(K[i:j], T[i:j], w, h)["t_hit"].numpy()
+        if volume:
+            depth = scene.ray_cast_frames(K[i:j], T[i:j], w, h, **{**cast_kw, "render_attributes": ("depth",),
+                                                                   "depth_scale": 1.0, "pixel_offset": 0.5,
+                                                                   "refine": True})["depth"].numpy()
+            depth[depth == 0] = np.inf
+        else:
+            depth = scene.cast_pinhole(K[i:j], T[i:j], w, h)["t_hit"].numpy()
         for k in range(j - i):
             yield depth[k]
         i = j
+
+
+def render_color_aligned_depth(scene_or_vbg, data_io, optimized_color_dataset_map=None,
+                               only_use_optimized_dataset: bool = False, sides=None, batch: int = 16, **cast_kw):
+    """The reference's colour-aligned-depth stage (reconstruct_scene.py:200-225): per side, one depth map per
+    colour frame through ``data_io.rgbd.save_color_aligned_depth`` -- the unoptimised frames whose timestamps
+    are not in the optimised set, then the optimised ones; without an optimised map, every frame unless
+    only_use_optimized_dataset.  The saves run on the I/O pool, so they overlap the next batch's cast.
+    Returns the number of maps written."""
+    from collections import deque
+    from ._io import io_pool
+    from .models import Side
+    pending = deque()  # saves in flight, oldest first: at most two batches' worth, so a slow disk holds the
+    written = 0        # casts back instead of letting the maps (4.9 MB each at 1280 x 960) pile up in memory
+
+    def render(dataset, side):
+        nonlocal written
+        maps = raycast_in_color_view(scene_or_vbg, dataset, batch=batch, **cast_kw)
+        for i in range(len(dataset)):
+            while len(pending) >= 2 * batch:  # before the next batch's cast: the batch before last is on disk
+                pending.popleft().result()
+            timestamp = dataset.timestamps[i]
+            depth_map = next(maps)
+            pending.append(io_pool().submit(data_io.rgbd.save_color_aligned_depth, depth_map=depth_map, side=side,
+                                            timestamp=timestamp))
+            written += 1
+
+    for side in (Side if sides is None else sides):
+        color_dataset = data_io.color.load_color_dataset(side=side, use_cache=True)
+        if optimized_color_dataset_map is not None:
+            optimized = optimized_color_dataset_map[side]
+            if not only_use_optimized_dataset:
+                optimized_timestamps = set(optimized.timestamps)
+                render(color_dataset[[i for i in range(len(color_dataset))
+                                      if color_dataset.timestamps[i] not in optimized_timestamps]], side)
+            render(optimized, side)
+        elif not only_use_optimized_dataset:
+            render(color_dataset, side)
+    while pending:
+        pending.popleft().result()
+    return written

@@ -12,6 +12,11 @@ refine_fragment_poses.py:39, reconstruction_data_io.py:42-55):
     .extract_point_cloud(weight_threshold=3.0, estimated_point_number=-1)
     .extract_triangle_mesh(weight_threshold=3.0, estimated_vertex_number=-1)
     .save(path) / VoxelBlockGrid.load(path)
+    .ray_cast(block_coords, intrinsic, extrinsic, width, height, render_attributes, depth_scale, depth_min,
+              depth_max, weight_threshold, trunc_voxel_multiplier, range_map_down_factor)
+                                      -> {"depth" (H,W,1), "vertex" (H,W,3), "normal" (H,W,3)}  (Open3D's
+                                      method, which the reference does not call; ``ray_cast_frames`` is its
+                                      batched form)
 
 plus ``integrate_frames`` (the batched whole-loop entry used by ``mqr.o3d_utils.integrate``).
 Every call goes through libmqr_hip.so; there is no CPU path.
@@ -279,6 +284,70 @@ class VoxelBlockGrid:
     def extract_triangle_mesh(self, weight_threshold=3.0, estimated_vertex_number=-1):
         """The mesh on the volume's device, as Open3D returns it (arrays in HBM until a host access)."""
         return TriangleMesh.from_device(self._geom("mqr_extract_mesh", weight_threshold), device=self.device)
+
+    # -- rendering ---------------------------------------------------------------------------------
+    _RENDER_ATTRIBUTES = ("depth", "vertex", "normal")
+
+    def ray_cast_frames(self, intrinsics, extrinsics, width, height, render_attributes=("depth",),
+                        depth_scale=_O3D_DEPTH_SCALE, depth_min=0.1, depth_max=_O3D_DEPTH_MAX, weight_threshold=3.0,
+                        trunc_voxel_multiplier=_O3D_TRUNC, range_map_down_factor=8, block_coords=None,
+                        pixel_offset=0.0, refine=False):
+        """Depth / vertex / normal maps of the fused surface for a stack of same-size cameras (intrinsics
+        (n,3,3), extrinsics (n,4,4) world -> camera), marched through the volume itself (csrc/volumecast.hip,
+        DESIGN.md §2.10): a dict of Tensors over device buffers, "depth" (n, H, W), "vertex" and "normal"
+        (n, H, W, 3), 0 where a ray hits nothing.  pixel_offset 0.5 casts the rays of
+        ``RaycastingScene.create_rays_pinhole``; refine re-interpolates each crossing trilinearly."""
+        from ._lib import DeviceBuffer
+        from .geometry import DeviceArray
+        attrs = tuple(render_attributes)
+        bad = [a for a in attrs if a not in self._RENDER_ATTRIBUTES]
+        if bad or not attrs:
+            raise ValueError(f"render_attributes must be among {self._RENDER_ATTRIBUTES} (the volume carries "
+                             f"no colour), got {attrs}")
+        K = np.ascontiguousarray(intrinsics, dtype=np.float64).reshape(-1, 3, 3)
+        T = np.ascontiguousarray(extrinsics, dtype=np.float64).reshape(-1, 4, 4)
+        if len(K) != len(T):
+            raise ValueError(f"{len(K)} intrinsics for {len(T)} extrinsics")
+        n, H, W = len(K), int(height), int(width)
+        keys, nk = None, 0
+        if block_coords is not None:
+            keys = np.ascontiguousarray(block_coords.numpy() if hasattr(block_coords, "numpy") else block_coords,
+                                        dtype=np.int32).reshape(-1, 3)
+            nk = keys.shape[0]
+            if nk == 0:  # an empty list (a non-null pointer, no rows) bounds nothing: all misses
+                keys = np.zeros((1, 3), np.int32)
+        outs = {}
+        for a in self._RENDER_ATTRIBUTES:
+            if a in attrs:
+                k = () if a == "depth" else (3,)
+                outs[a] = (DeviceBuffer(max(4, 4 * max(n, 0) * max(H, 0) * max(W, 0) * (3 if k else 1)),
+                                        self.device_id), k)
+        p = {a: (outs[a][0].ptr if a in outs else None) for a in self._RENDER_ATTRIBUTES}
+        call("mqr_vbg_ray_cast", self._h, None if keys is None else ptr(keys), nk, MQR_HOST, ptr(K, _lib._f64p),
+             ptr(T, _lib._f64p), n, H, W, float(depth_scale), float(depth_min), float(depth_max),
+             float(weight_threshold), float(trunc_voxel_multiplier), int(range_map_down_factor), float(pixel_offset),
+             1 if refine else 0, p["depth"], p["vertex"], p["normal"], MQR_DEVICE)
+        return {a: Tensor(DeviceArray(buf, buf.ptr.value, (n, H, W) + k, np.float32, self.device_id))
+                for a, (buf, k) in outs.items()}
+
+    def ray_cast(self, block_coords, intrinsic, extrinsic, width, height, render_attributes=("depth",),
+                 depth_scale=_O3D_DEPTH_SCALE, depth_min=0.1, depth_max=_O3D_DEPTH_MAX, weight_threshold=3.0,
+                 trunc_voxel_multiplier=_O3D_TRUNC, range_map_down_factor=8):
+        """Open3D's ``VoxelBlockGrid.ray_cast`` (its argument order and defaults): a dict with "depth" (H, W, 1),
+        "vertex" and "normal" (H, W, 3) as asked for.  block_coords=None: every active block."""
+        r = self.ray_cast_frames(_mat(intrinsic, (3, 3)), _mat(extrinsic, (4, 4)), width, height, render_attributes,
+                                 depth_scale, depth_min, depth_max, weight_threshold, trunc_voxel_multiplier,
+                                 range_map_down_factor, block_coords=block_coords)
+        from .geometry import DeviceArray
+        H, W = int(height), int(width)
+        return {a: Tensor(DeviceArray(t.device_array().owner, t.device_array().ptr, (H, W, 1 if a == "depth" else 3),
+                                      np.float32, self.device_id)) for a, t in r.items()}
+
+    def ray_cast_last_ms(self):
+        """(range map, march) device time of the last ray cast on this volume's device, ms."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        call("mqr_vbg_ray_cast_last_ms", self._h, ctypes.byref(a), ctypes.byref(b))
+        return a.value, b.value
 
     # -- contents ----------------------------------------------------------------------------------
     def export(self):

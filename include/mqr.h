@@ -87,6 +87,14 @@ int mqr_device_mem_info(int device, int64_t* free_bytes, int64_t* total_bytes);
  * -- reference call site scripts/processing/reconstruction/utils/o3d_utils.py:170-179.
  * block_count is the initial capacity; the volume grows automatically like Open3D's hash map. */
 int mqr_vbg_create(float voxel_size, int block_resolution, int64_t block_count, int device, mqr_vbg** out);
+/* The same volume with Open3D's attr_names=('tsdf','weight','color') layout: one more attribute per voxel,
+ * three float32 channels in 0..255, every channel 0 whenever a block is allocated or the volume is reset
+ * (DESIGN.md 2.11).  block_resolution must be 8 or 16 (else status 2).  Costs 20 bytes per voxel instead of 8.
+ * A coloured volume's mqr_vbg_reset never swaps sets: it queues behind an unfinished integrate.  The multi-GPU
+ * merge (mqr_vbg_pack_weighted / unpack_weighted, mqr_reduce_rccl, mqr_merge_local, mqr_xchg_*) and
+ * mqr_extract_mesh_owned refuse a coloured volume with status 2. */
+int mqr_vbg_create_color(float voxel_size, int block_resolution, int64_t block_count, int device, mqr_vbg** out);
+int mqr_vbg_has_color(mqr_vbg* v, int* has_color);
 int mqr_vbg_destroy(mqr_vbg* v);
 /* Empty the volume in place (keeps its allocations): the state of a freshly created grid.  Ordered on the
  * device: when an integrate of an asynchronously returning mqr_integrate_frames is still in flight, the
@@ -122,10 +130,36 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
                          const double* T_wc, const uint8_t* frame_ok, float depth_scale, float depth_max,
                          float trunc_mult);
 
+/* Open3D's colour integrate: vbg.integrate(block_coords, depth, color, depth_intrinsic, color_intrinsic,
+ * extrinsic, ...).  The (tsdf, weight) update is mqr_integrate's / mqr_integrate_frames', bit for bit; a voxel
+ * that accepts a frame and projects into the colour image (its own intrinsic K_color, the depth's extrinsic)
+ * also averages that pixel into its colour with the weight before the update.
+ * colors: uint8 [B][Hc][Wc][3] (one frame for mqr_integrate_color), color_loc MQR_HOST or MQR_DEVICE; K_color B*9.
+ * Host colour frames are staged per batch as host depth frames are.  With depth and colour both MQR_DEVICE the
+ * call orders itself behind the caller stream and returns with the last integrate queued, the caller stream
+ * made to wait for it, as mqr_integrate_frames does; otherwise it returns when the work has finished
+ * (MQR_DEVICE_RESIDENT is not accepted).  A volume without colour, a null pointer, Hc or Wc <= 0, a non-finite
+ * K_color or one with a zero focal length: status 2, nothing launched.  The depth-only calls stay legal on a
+ * coloured volume and leave its colours alone. */
+int mqr_integrate_color(mqr_vbg* v, const int32_t* keys, int64_t n, const float* depth, int depth_loc, int H, int W,
+                        const uint8_t* color, int color_loc, int Hc, int Wc, const double* K_depth,
+                        const double* K_color, const double* T_wc, float depth_scale, float depth_max,
+                        float trunc_mult);
+int mqr_integrate_frames_color(mqr_vbg* v, const float* depths, int depth_loc, int B, int H, int W,
+                               const uint8_t* colors, int color_loc, int Hc, int Wc, const double* K_depth,
+                               const double* K_color, const double* T_wc, const uint8_t* frame_ok, float depth_scale,
+                               float depth_max, float trunc_mult);
+
 /* Volume contents (VoxelBlockGrid.save / load payload, and the multi-GPU merge).  Blocks are in
  * buffer order: keys n*3 int32, tsdf / weight n*R^3 float32 ([z][y][x] within a block). */
 int mqr_vbg_export(mqr_vbg* v, int32_t* keys, float* tsdf, float* weight, int loc);
 int mqr_vbg_import(mqr_vbg* v, const int32_t* keys, const float* tsdf, const float* weight, int64_t n, int loc);
+/* Colours of a coloured volume: n*R^3*3 float32, [block][voxel][channel] with the blocks in mqr_vbg_export's
+ * order, whatever the pool's own layout.  import_color writes the colours of the blocks `keys` names (blocks
+ * the volume does not hold are skipped); mqr_vbg_import itself leaves the colours of the blocks it allocates
+ * at zero.  A volume without colour: status 2. */
+int mqr_vbg_export_color(mqr_vbg* v, float* colors, int loc);
+int mqr_vbg_import_color(mqr_vbg* v, const int32_t* keys, const float* colors, int64_t n, int loc);
 
 /* Multi-GPU merge: pack the volume against a shared, sorted union key table into
  * [U][R^3][2] = (weight*tsdf, weight) float32 (zeros where a block is absent), and the inverse
@@ -217,8 +251,9 @@ int mqr_geom_free(mqr_geom* g);
  * on a CUDA device stays there, and hand it to MQR_DEVICE inputs (mqr_scene_add_triangles,
  * mqr_mesh_filter_components, mqr_color_map) without a host round trip. */
 int mqr_geom_device_ptrs(mqr_geom* g, void** positions, void** normals, void** triangles);
-/* Vertex colours of a result (float32 [nv][3]).  Only mqr_mesh_simplify_clustering on a coloured input makes
- * them: for every other producer device_colors reports a null pointer and copy_colors is status 2.
+/* Vertex colours of a result (float32 [nv][3], 0..1).  mqr_extract_points / mqr_extract_mesh on a coloured
+ * volume (mqr_vbg_create_color) and mqr_mesh_simplify_clustering on a coloured input make them: for every
+ * other producer device_colors reports a null pointer and copy_colors is status 2.
  * device_colors: the array in place, as mqr_geom_device_ptrs.  copy_colors: nv*3 float32 into `loc` memory. */
 int mqr_geom_device_colors(mqr_geom* g, void** colors);
 int mqr_geom_copy_colors(mqr_geom* g, float* colors, int loc);
@@ -735,6 +770,16 @@ int mqr_vbg_ray_cast(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int 
                      const double* T_wc, int n, int H, int W, float depth_scale, float depth_min, float depth_max,
                      float weight_threshold, float trunc_voxel_multiplier, int range_map_down_factor,
                      float pixel_offset, int flags, float* depth, float* vertex, float* normal, int out_loc);
+/* The same call with a colour map beside the others (nullable like them): float32 [n][H][W][3] in 0..1, the
+ * colours of the 8 lattice corners around the hit vertex that exist and have weight > 0, weighted by the
+ * trilinear fractions and renormalised; 0 on a miss or when no corner counts.  A colour output
+ * on a volume without colour: status 2.  mqr_vbg_ray_cast is this call with color = NULL (it keeps its argument
+ * list: existing callers pass 21 arguments). */
+int mqr_vbg_ray_cast_color(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int keys_loc, const double* K,
+                           const double* T_wc, int n, int H, int W, float depth_scale, float depth_min,
+                           float depth_max, float weight_threshold, float trunc_voxel_multiplier,
+                           int range_map_down_factor, float pixel_offset, int flags, float* depth, float* vertex,
+                           float* normal, float* color, int out_loc);
 /* Device time (events on the volume's stream) of the last ray cast on the volume's device: the range map and
  * the march, ms. */
 int mqr_vbg_ray_cast_last_ms(mqr_vbg* v, double* range_ms, double* march_ms);

@@ -662,6 +662,21 @@ __device__ inline float mc_tsdf(const int32_t* __restrict__ nbrow, const float2*
     return pool[(int64_t)nbuf * M::R3 + ((z - dz * R) * R + (y - dy * R)) * R + (x - dx * R)].x;
 }
 
+// Colour of the vertex on the edge from tile point (x, y, z) along `axis`: per channel
+// ((1 - ratio) c_o + ratio c_e) / 255 from the planar colour pool ([buf][3][R^3]), ratio the vertex's own.
+template <class M>
+__device__ inline void mc_edge_color(const int32_t* __restrict__ nbrow, const float* __restrict__ cpool, int x, int y,
+                                     int z, int axis, float ratio, float* __restrict__ out) {
+    constexpr int R = M::C - 1;
+    const int ex = x + (axis == 0), ey = y + (axis == 1), ez = z + (axis == 2);
+    const int dx = M::blk(ex), dy = M::blk(ey), dz = M::blk(ez);
+    const float* co = cpool + (int64_t)nbrow[13] * (3 * M::R3) + (z * R + y) * R + x;  // (the origin is the block's own)
+    const float* ce = cpool + (int64_t)nbrow[(dx + 1) + 3 * (dy + 1) + 9 * (dz + 1)] * (3 * M::R3) +
+                      ((ez - dz * R) * R + (ey - dy * R)) * R + (ex - dx * R);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = ((1 - ratio) * co[c * M::R3] + ratio * ce[c * M::R3]) / 255.0f;
+}
+
 // Central-difference normal at tile point (x, y, z), components left untouched where a side's
 // block is absent (upstream DeviceGetNormal; presence is per block: bit k27 of pres).
 template <class M>
@@ -762,10 +777,11 @@ __device__ __forceinline__ int row_search(const uint4* rows, int i) {
     return lo;
 }
 
-template <class M>
+template <class M, bool COLOR>
 __device__ __forceinline__ void mc_emit_vertex(int i, int lo, const uint4* rows, const int32_t* nbrow,
                                                const float2* __restrict__ pool, uint32_t pres, int xb, int yb, int zb,
-                                               float voxel_size, int32_t vb0, float* pos, float* nrm) {
+                                               float voxel_size, int32_t vb0, float* pos, float* nrm,
+                                               const float* __restrict__ cpool, float* col) {
     constexpr int R = M::C - 1;
     const uint4 rw = rows[lo];
     const uint32_t ex = rw.z & 0xffffu, ey = rw.z >> 16, ez = rw.w & 0xffffu;
@@ -805,6 +821,7 @@ __device__ __forceinline__ void mc_emit_vertex(int i, int lo, const uint4* rows,
     const float ny = (1 - ratio) * no[1] + ratio * ne[1];
     const float nz = (1 - ratio) * no[2] + ratio * ne[2];
     write_normal(nx, ny, nz, nrm + 3 * id);
+    if constexpr (COLOR) mc_edge_color<M>(nbrow, cpool, x, y, z, axis, ratio, col + 3 * id);
 }
 
 // Triangle i of a block (emission pass): its cube by binary search over the row triangle bases and a
@@ -882,14 +899,15 @@ __device__ __forceinline__ void mc_emit_tri(int i, int lo, const uint4* rows, co
 // D2H copy enqueued between the scan and this pass, whose latency this pass waited behind.)
 constexpr int kRowMap = 2048;
 
-template <int R, int NT>
+template <int R, int NT, bool COLOR>
 __device__ __forceinline__ void mc_emit_block(int64_t b, const int32_t* __restrict__ nb,
                                               const uint64_t* __restrict__ bkeys, const float2* __restrict__ pool,
                                               float voxel_size, const int32_t* __restrict__ vcount,
                                               const int32_t* __restrict__ tcount, const int32_t* __restrict__ voff,
                                               const int32_t* __restrict__ toff, const uint4* __restrict__ rows4,
                                               const uint32_t* __restrict__ rowNt, float* pos, float* nrm, int32_t* tri,
-                                              int64_t cap_v, int64_t cap_t, const uint64_t* __restrict__ rowsT) {
+                                              int64_t cap_v, int64_t cap_t, const uint64_t* __restrict__ rowsT,
+                                              const float* __restrict__ cpool, float* col) {
     using M = Mc<R, 1>;
     static_assert(NT >= 256, "one thread per triangle-table row");
     static_assert(M::R2 <= 256, "row ids in bytes");
@@ -937,7 +955,7 @@ __device__ __forceinline__ void mc_emit_block(int64_t b, const int32_t* __restri
         unpack_key(bkeys[b], xb, yb, zb);
         for (int i = tid; i < nvb; i += NT) {
             const int lo = vm ? (int)vmap[i] : row_search<M::R2, 0>(rows, i);
-            mc_emit_vertex<M>(i, lo, rows, nbrow, pool, pres, xb, yb, zb, voxel_size, vb0, pos, nrm);
+            mc_emit_vertex<M, COLOR>(i, lo, rows, nbrow, pool, pres, xb, yb, zb, voxel_size, vb0, pos, nrm, cpool, col);
         }
     }
     for (int i = tid; i < ntb; i += NT) {
@@ -946,16 +964,19 @@ __device__ __forceinline__ void mc_emit_block(int64_t b, const int32_t* __restri
     }
 }
 
-template <int R, int NT = kMcThreads>
+// COLOR: the volume carries colour -- vertex colours from cpool into col (mc_edge_color); the colourless
+// instantiation compiles none of it.
+template <int R, bool COLOR = false, int NT = kMcThreads>
 __global__ __launch_bounds__(NT) void k_mc_emit(const int32_t* __restrict__ nb, const uint64_t* __restrict__ bkeys,
                                                 const float2* __restrict__ pool, float voxel_size,
                                                 const int32_t* __restrict__ vcount, const int32_t* __restrict__ tcount,
                                                 const int32_t* __restrict__ voff, const int32_t* __restrict__ toff,
                                                 const uint4* __restrict__ rows4, const uint32_t* __restrict__ rowNt,
                                                 float* pos, float* nrm, int32_t* tri, int64_t cap_v, int64_t cap_t,
-                                                const uint64_t* __restrict__ rowsT) {
-    mc_emit_block<R, NT>(blockIdx.x, nb, bkeys, pool, voxel_size, vcount, tcount, voff, toff, rows4, rowNt, pos, nrm,
-                         tri, cap_v, cap_t, rowsT);
+                                                const uint64_t* __restrict__ rowsT,
+                                                const float* __restrict__ cpool, float* col) {
+    mc_emit_block<R, NT, COLOR>(blockIdx.x, nb, bkeys, pool, voxel_size, vcount, tcount, voff, toff, rows4, rowNt, pos,
+                                nrm, tri, cap_v, cap_t, rowsT, cpool, col);
 }
 
 // (A decoupled look-back inside the count pass, one word per step or 64 per step, made the C2 count
@@ -1099,13 +1120,13 @@ __global__ __launch_bounds__(kMcThreads) void k_pt_count(const int32_t* __restri
 // Points in (block, voxel, axis) order: position voxel_size (X + ratio e), normal interpolated
 // between the central-difference normals at o and q (the q-normal scratch carried across the
 // voxel's point axes, as upstream's per-voxel ni).
-template <int R>
+template <int R, bool COLOR = false>
 __global__ __launch_bounds__(kMcThreads) void k_pt_emit(const int32_t* __restrict__ nb, const uint64_t* __restrict__ bkeys,
                                                         const float2* __restrict__ pool, float voxel_size,
                                                         const int32_t* __restrict__ count,
                                                         const int32_t* __restrict__ off,
                                                         const uint4* __restrict__ rows4, float* pos, float* nrm,
-                                                        int64_t cap) {
+                                                        int64_t cap, const float* __restrict__ cpool, float* col) {
     using M = Mc<R, 1>;
     __shared__ uint4 rows[M::R2];
     __shared__ int32_t nbrow[27];
@@ -1165,6 +1186,7 @@ __global__ __launch_bounds__(kMcThreads) void k_pt_emit(const int32_t* __restric
         const float ny = (1 - ratio) * no[1] + ratio * ni[1];
         const float nz = (1 - ratio) * no[2] + ratio * ni[2];
         write_normal(nx, ny, nz, nrm + 3 * id);
+        if constexpr (COLOR) mc_edge_color<M>(nbrow, cpool, x, y, z, axis, ratio, col + 3 * id);
     }
 }
 
@@ -1301,7 +1323,7 @@ template <class Emit>
 static int emit_sized(mqr_vbg* v, mqr_geom* g, bool mesh, int64_t* hint, Emit emit) {
     const int64_t cv = hint ? spec_cap(hint[0]) : 0, ct = hint && mesh ? spec_cap(hint[1]) : 0;
     const bool spec = cv > 0 && (ct > 0 || !mesh);
-    if (spec && geom_alloc(g, cv, ct)) return 1;
+    if (spec && geom_alloc(g, cv, ct, v->has_color)) return 1;
     MQR_CHECK_HIP(hipGetLastError());
     if (spec) {
         emit(cv, ct);
@@ -1322,7 +1344,7 @@ static int emit_sized(mqr_vbg* v, mqr_geom* g, bool mesh, int64_t* hint, Emit em
         geom_block_release(g->device, g->blk, g->blk_cap);
         g->blk = nullptr;
     }
-    if (geom_alloc(g, nv, nt)) return 1;
+    if (geom_alloc(g, nv, nt, v->has_color)) return 1;
     emit(nv, nt);
     MQR_CHECK_HIP(hipGetLastError());
     MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
@@ -1342,9 +1364,10 @@ static int mesh_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g, i
                            e.c0, e.c1, rows4, rowNt, rowsT);
         scan_counts(v, e, n, true);
         return emit_sized(v, g, true, v->ex_hint, [&](int64_t cap_v, int64_t cap_t) {
-            hipLaunchKernelGGL(k_mc_emit<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys, v->pool,
+            auto kern = v->has_color ? k_mc_emit<RT, true> : k_mc_emit<RT, false>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys, v->pool,
                                v->voxel_size, e.c0, e.c1, e.o0, e.o1, rows4, rowNt, g->pos, g->nrm, g->tri, cap_v,
-                               cap_t, rowsT);
+                               cap_t, rowsT, v->cpool, g->col);
         });
     } else {
         if (build_nb(v, e.nb)) return 1;
@@ -1370,8 +1393,9 @@ static int point_passes(mqr_vbg* v, float thr, const ExScratch& e, mqr_geom* g) 
                            e.c0, rows4);
         scan_counts(v, e, n, false);
         return emit_sized(v, g, false, v->ex_hint + 2, [&](int64_t cap, int64_t) {
-            hipLaunchKernelGGL(k_pt_emit<RT>, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys,
-                               v->pool, v->voxel_size, e.c0, e.o0, rows4, g->pos, g->nrm, cap);
+            auto kern = v->has_color ? k_pt_emit<RT, true> : k_pt_emit<RT, false>;
+            hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(kMcThreads), 0, v->stream, e.nb, v->bkeys, v->pool,
+                               v->voxel_size, e.c0, e.o0, rows4, g->pos, g->nrm, cap, v->cpool, g->col);
         });
     } else {
         if (build_nb(v, e.nb)) return 1;
@@ -1399,6 +1423,7 @@ static int extract(mqr_vbg* v, float thr, bool mesh, int64_t n_owned, mqr_geom**
     // (at R = 1 the tile [-1, R + 1] would reach two blocks away)
     MQR_REQUIRE(v->R >= 2, name + " needs block_resolution >= 2, got " + std::to_string(v->R));
     MQR_REQUIRE(n_owned < 0 || v->R == 16 || v->R == 8, "owned-block extraction supports block_resolution 8 / 16");
+    MQR_REQUIRE(n_owned < 0 || !v->has_color, "owned-block extraction of a coloured volume is not supported");
     const int64_t tri_blocks = n_owned < 0 ? INT64_MAX : n_owned;
     MQR_CHECK_HIP(hipSetDevice(v->device));
     if (order_after_integrate(v)) return 1;  // an integrate may still be running on the second stream

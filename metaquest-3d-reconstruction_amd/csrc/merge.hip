@@ -797,6 +797,7 @@ int mqr_comm_counts(mqr_comm* c, int64_t* send_blocks, int64_t* recv_blocks, int
 int mqr_reduce_rccl(mqr_vbg* local, mqr_comm* c, int mode, int root, mqr_vbg* out, int64_t* n_owned) {
     MQR_REQUIRE(local && c && out && n_owned, "null argument");
     MQR_REQUIRE(local != out, "mqr_reduce_rccl: `out` must be a different volume than `local` (it is emptied first)");
+    MQR_REQUIRE(!local->has_color && !out->has_color, "mqr_reduce_rccl: merging a coloured volume is not supported");
     MQR_REQUIRE(mode == MQR_MERGE_ROOT || mode == MQR_MERGE_SHARDED, "unknown merge mode");
     MQR_REQUIRE(root >= 0 && root < c->world, "root out of range");
     MQR_REQUIRE(local->device == c->device && out->device == c->device, "volumes and communicator on one device");
@@ -887,6 +888,8 @@ int mqr_merge_local(mqr_vbg** locals, int n, int mode, int root, mqr_vbg** outs,
     MQR_REQUIRE(root >= 0 && root < n, "root out of range");
     for (int r = 0; r < n; ++r) {
         MQR_REQUIRE(locals[r] && outs[r], "null volume");
+        MQR_REQUIRE(!locals[r]->has_color && !outs[r]->has_color,
+                    "mqr_merge_local: merging a coloured volume is not supported");
         MQR_REQUIRE(locals[r]->device == locals[0]->device && outs[r]->device == locals[0]->device,
                     "mqr_merge_local: all volumes on one device");
         MQR_REQUIRE(locals[r]->R == locals[0]->R && outs[r]->R == locals[0]->R &&
@@ -1005,6 +1008,7 @@ int mqr_xchg_create(mqr_vbg* local, int world, int rank, int mode, int root, con
                     int64_t mx, int keys_loc, mqr_vbg* out, mqr_xchg** h) {
     MQR_REQUIRE(local && out && gathered_keys && h, "null argument");
     MQR_REQUIRE(local != out, "mqr_xchg_create: `out` must be a different volume than `local` (it is emptied first)");
+    MQR_REQUIRE(!local->has_color && !out->has_color, "mqr_xchg_create: merging a coloured volume is not supported");
     MQR_REQUIRE(world >= 1 && world <= kMaxRanks && rank >= 0 && rank < world, "rank / world out of range (world <= 64)");
     MQR_REQUIRE(mode == MQR_MERGE_ROOT || mode == MQR_MERGE_SHARDED, "unknown merge mode");
     MQR_REQUIRE(root >= 0 && root < world, "root out of range");

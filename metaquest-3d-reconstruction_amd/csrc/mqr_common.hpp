@@ -105,6 +105,13 @@ struct FrameParams {
 
 void make_frame_params(const double* K, const double* T_wc, FrameParams* fp);
 
+// Per-frame parameters of the colour pass (k_integrate_color): the colour intrinsics as float32 and the
+// frame's index in the colour stack the kernel is given.
+struct ColorFrame {
+    float fx, fy, cx, cy;
+    int64_t frame;
+};
+
 // frames per device batch (one bit each in the slot mask); the first batch of a call is a full batch too --
 // a 64-frame first batch starts the first integrate sooner but adds a launch (2.551 vs 2.499 ms per C2
 // step, profiles/r04_ab_integrate.json)
@@ -158,6 +165,20 @@ struct mqr_vbg {
     uint64_t* bkeys = nullptr; // [pool_cap] packed key of each buffer
     int64_t pool_cap = 0;
     int64_t pool_count = 0;    // host mirror (valid after each batch)
+    // Colour attribute (mqr_vbg_create_color): three float32 channels per voxel, planar per
+    // block, indexed by the same buffer index as pool.  It follows the pool's growth; a coloured volume
+    // declines the set swap of mqr_vbg_reset (its reset queues behind the integrate instead).
+    bool has_color = false;
+    float* cpool = nullptr;    // [pool_cap][3][R3]
+    mqr::ColorFrame* d_cfp[2] = {nullptr, nullptr};  // colour frame parameters of a batch ([kMaxBatch])
+    mqr::ColorFrame* h_cfp[2] = {nullptr, nullptr};  // pinned mirrors
+    uint8_t* d_color[2] = {nullptr, nullptr};        // staging for host colour frames
+    int64_t color_cap = 0;                           // bytes per parity
+    // the colour stack of the batch being launched (launch_integrate runs the colour pass when base is set)
+    struct ColorIn {
+        const uint8_t* base = nullptr;
+        int Hc = 0, Wc = 0;
+    } col_in;
     // Upper bound of any voxel's weight (every integrated frame adds at most 1): the merge sends weights as
     // uint16 when every rank's bound is <= 65535.  -1 = unknown (imported or unpacked contents).
     int64_t wbound = 0;
@@ -242,7 +263,7 @@ struct mqr_geom {
     float* pos = nullptr;
     float* nrm = nullptr;
     int32_t* tri = nullptr;
-    float* col = nullptr;  // vertex colours (meshsimplify.hip); null for every other producer
+    float* col = nullptr;  // vertex colours (meshsimplify.hip, extract.hip on a coloured volume); else null
     void* blk = nullptr;  // when set, pos / nrm / tri (/ col) are carved from this one allocation
     size_t blk_cap = 0;   // its size (a recycled block may be larger than needed)
 };

@@ -193,6 +193,14 @@ int grow_pool(mqr_vbg* v, int64_t need) {
     uint64_t* nk = nullptr;
     MQR_CHECK_HIP(hipMalloc(&np, sizeof(float2) * ncap * v->R3));
     MQR_CHECK_HIP(hipMalloc(&nk, sizeof(uint64_t) * ncap));
+    float* nc = nullptr;
+    if (v->has_color) {  // the colour pool follows the pool (48 KiB per block at R = 16: sized in 64 bits)
+        const size_t block_bytes = sizeof(float) * 3 * (size_t)v->R3;
+        MQR_CHECK_HIP(hipMalloc(&nc, block_bytes * (size_t)ncap));
+        if (v->pool_cap)
+            MQR_CHECK_HIP(hipMemcpyAsync(nc, v->cpool, block_bytes * (size_t)v->pool_cap, hipMemcpyDeviceToDevice,
+                                         v->stream));
+    }
     if (v->pool_cap) {  // buffers past the old capacity are not cleared (see mqr_vbg_reset)
         MQR_CHECK_HIP(hipMemcpyAsync(np, v->pool, sizeof(float2) * v->pool_cap * v->R3, hipMemcpyDeviceToDevice,
                                      v->stream));
@@ -202,8 +210,10 @@ int grow_pool(mqr_vbg* v, int64_t need) {
     MQR_CHECK_HIP(hipStreamSynchronize(v->stream));
     if (v->pool) MQR_CHECK_HIP(hipFree(v->pool));
     if (v->bkeys) MQR_CHECK_HIP(hipFree(v->bkeys));
+    if (v->cpool) MQR_CHECK_HIP(hipFree(v->cpool));
     v->pool = np;
     v->bkeys = nk;
+    v->cpool = nc;
     v->pool_cap = ncap;
     return 0;
 }
@@ -452,6 +462,30 @@ static int launch_integrate(mqr_vbg* v, int p, const float* depths, int64_t HW, 
     const int32_t* bad_list = v->bad[p];
     const bmask_t* bad_mask = reinterpret_cast<const bmask_t*>(v->bad[p] + v->list_cap);
     int* bad_count = counters + kBadCount;
+    if (v->col_in.base) {
+        // the colour pass, directly before the batch's tsdf kernel(s): it reads the weights
+        // the pool holds before the batch and writes colours only, from the same list, masks and counters
+        // (the shadow set of a speculative launch: a batch an empty frame aborts colours nothing)
+        const ColorFrame* cfs = v->d_cfp[p];
+        if (v->R == 16)
+            // (1024 threads, 4 voxels each: 51 VGPRs, 8 waves per SIMD; 512 x 8 takes 74 and gets 6, 256 x 16
+            // takes 120 and gets 4 -- the pass waits on gathers, so the occupancy decides)
+            hipLaunchKernelGGL((k_integrate_color<16, 1024>), dim3(grid), dim3(1024), 0, s, list, lmask,
+                               counters + kListCount, v->list_cap, t, v->pool, v->cpool, v->voxel_size, depths, HW, H,
+                               W, fp, depth_frame, depth_scale, depth_max, sdf_trunc, first_new, v->col_in.base,
+                               v->col_in.Hc, v->col_in.Wc, cfs);
+        else
+            hipLaunchKernelGGL((k_integrate_color<8, 256>), dim3(grid), dim3(256), 0, s, list, lmask,
+                               counters + kListCount, v->list_cap, t, v->pool, v->cpool, v->voxel_size, depths, HW, H,
+                               W, fp, depth_frame, depth_scale, depth_max, sdf_trunc, first_new, v->col_in.base,
+                               v->col_in.Hc, v->col_in.Wc, cfs);
+    }
+    else if (v->has_color && spec == 0 && v->pool_count > first_new) {
+        // a depth-only batch on a coloured volume: the blocks it allocated start without colour
+        const size_t block_bytes = sizeof(float) * 3 * (size_t)v->R3;
+        MQR_CHECK_HIP(hipMemsetAsync(v->cpool + (size_t)first_new * 3 * (size_t)v->R3, 0,
+                                     block_bytes * (size_t)(v->pool_count - first_new), s));
+    }
     bool fixup = false;  // the exact fix-up launch over the blocks a fast kernel handed back
     if (var == 1) {
         hipLaunchKernelGGL(k_integrate, dim3(grid), dim3(256), 0, s, list, counters, v->list_cap, t, v->pool, v->R,
@@ -797,8 +831,11 @@ int mqr_device_synchronize(int device) {
     return 0;
 }
 
-int mqr_vbg_create(float voxel_size, int block_resolution, int64_t block_count, int device, mqr_vbg** out) {
+static int create_volume(float voxel_size, int block_resolution, int64_t block_count, int device, bool color,
+                         mqr_vbg** out) {
     MQR_REQUIRE(out, "out is NULL");
+    MQR_REQUIRE(!color || block_resolution == 8 || block_resolution == 16,
+                "a coloured volume needs block_resolution 8 or 16");
     MQR_REQUIRE(voxel_size > 0.f, "voxel_size must be positive");
     MQR_REQUIRE(block_resolution >= 1 && block_resolution <= 64, "block_resolution must be in [1, 64]");
     MQR_REQUIRE(block_count >= 1, "block_count must be positive");
@@ -811,6 +848,7 @@ int mqr_vbg_create(float voxel_size, int block_resolution, int64_t block_count, 
     v->voxel_size = voxel_size;
     v->R = block_resolution;
     v->R3 = (int64_t)block_resolution * block_resolution * block_resolution;
+    v->has_color = color;
     const size_t nctr = kCounterInts;
     // The touch stream gets the device's highest priority: touch(b+1) shares the CUs with
     // integrate(b), and integrate(b+1) cannot be enqueued before the host has read touch(b+1)'s
@@ -828,6 +866,9 @@ int mqr_vbg_create(float voxel_size, int block_resolution, int64_t block_count, 
              hipEventCreateWithFlags(&v->ev_int[p], hipEventDisableTiming | hipEventDisableSystemFence) ==
                  hipSuccess &&
              hipEventCreateWithFlags(&v->ev_host[p], hipEventDisableTiming) == hipSuccess;
+    for (int p = 0; p < 2 && ok && color; ++p)
+        ok = hipMalloc(&v->d_cfp[p], sizeof(ColorFrame) * kMaxBatch) == hipSuccess &&
+             hipHostMalloc(&v->h_cfp[p], sizeof(ColorFrame) * kMaxBatch, hipHostMallocDefault) == hipSuccess;
     if (!ok) {
         set_error("mqr_vbg_create: device allocation failed");
         mqr_vbg_destroy(v);
@@ -838,6 +879,20 @@ int mqr_vbg_create(float voxel_size, int block_resolution, int64_t block_count, 
         return 1;
     }
     *out = v;
+    return 0;
+}
+
+int mqr_vbg_create(float voxel_size, int block_resolution, int64_t block_count, int device, mqr_vbg** out) {
+    return create_volume(voxel_size, block_resolution, block_count, device, false, out);
+}
+
+int mqr_vbg_create_color(float voxel_size, int block_resolution, int64_t block_count, int device, mqr_vbg** out) {
+    return create_volume(voxel_size, block_resolution, block_count, device, true, out);
+}
+
+int mqr_vbg_has_color(mqr_vbg* v, int* has_color) {
+    MQR_REQUIRE(v && has_color, "null argument");
+    *has_color = v->has_color ? 1 : 0;
     return 0;
 }
 
@@ -857,7 +912,11 @@ int mqr_vbg_destroy(mqr_vbg* v) {
     if (v->mask1) (void)hipFree(v->mask1);
     if (v->pool) (void)hipFree(v->pool);
     if (v->bkeys) (void)hipFree(v->bkeys);
+    if (v->cpool) (void)hipFree(v->cpool);
     for (int p = 0; p < 2; ++p) {
+        if (v->d_cfp[p]) (void)hipFree(v->d_cfp[p]);
+        if (v->h_cfp[p]) (void)hipHostFree(v->h_cfp[p]);
+        if (v->d_color[p]) (void)hipFree(v->d_color[p]);
         if (v->lists[p]) (void)hipFree(v->lists[p]);
         if (v->lpt[p]) (void)hipFree(v->lpt[p]);
         if (v->bad[p]) (void)hipFree(v->bad[p]);
@@ -965,7 +1024,9 @@ int mqr_vbg_reset(mqr_vbg* v) {
     uint32_t segs = 0x1f;  // every counter segment (k_reset_table)
     const bool inflight = v->int_pending[0] || v->int_pending[1];
     bool flip = false;
-    if (inflight && ensure_alt(v, &flip)) return 1;
+    // (a coloured volume declines the swap: its colour pool has no second set, the clear queues behind the
+    // integrate instead)
+    if (inflight && !v->has_color && ensure_alt(v, &flip)) return 1;
     if (flip) {
         // an integrate of the current set is still in flight (mqr_integrate_frames on device frames returns
         // before it ends): mark the set's last reader on the integrate stream and swap in the other set,
@@ -1022,13 +1083,58 @@ int mqr_vbg_params(mqr_vbg* v, float* voxel_size, int* R, int* device) {
     return 0;
 }
 
-int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, int H, int W, const double* K,
-                         const double* T_wc, const uint8_t* frame_ok, float depth_scale, float depth_max,
-                         float trunc_mult) {
+// The colour stack of a coloured integrate call (null: depth only).
+struct ColorStack {
+    const uint8_t* frames;  // [B][Hc][Wc][3]
+    int loc, Hc, Wc;
+    const double* K;  // [B][9]
+};
+
+static int ensure_color_staging(mqr_vbg* v, int64_t bytes) {
+    if (v->color_cap >= bytes) return 0;
+    if (sync_all(v)) return 1;
+    for (int p = 0; p < 2; ++p) {
+        if (v->d_color[p]) MQR_CHECK_HIP(hipFree(v->d_color[p]));
+        v->d_color[p] = nullptr;
+        MQR_CHECK_HIP(hipMalloc(&v->d_color[p], (size_t)bytes));
+    }
+    v->color_cap = bytes;
+    return 0;
+}
+
+// Validation of a colour stack, before any launch.
+static int check_color_stack(const mqr_vbg* v, const ColorStack& c, int B) {
+    MQR_REQUIRE(v->has_color, "the volume carries no colour (mqr_vbg_create_color)");
+    MQR_REQUIRE(c.frames && c.K, "null argument");
+    MQR_REQUIRE(c.Hc > 0 && c.Wc > 0, "bad colour frame shape");
+    MQR_REQUIRE(c.loc == MQR_HOST || c.loc == MQR_DEVICE, "color_loc must be MQR_HOST or MQR_DEVICE");
+    for (int i = 0; i < B; ++i) {
+        const double* k = c.K + 9 * i;
+        for (int j = 0; j < 9; ++j) MQR_REQUIRE(std::isfinite(k[j]), "K_color is not finite");
+        MQR_REQUIRE((float)k[0] != 0.f && (float)k[4] != 0.f, "K_color has a zero focal length");
+    }
+    return 0;
+}
+
+// Clears the batch's colour stack when the integrate call leaves, on every path.
+struct ColorInScope {
+    mqr_vbg* v;
+    ~ColorInScope() { v->col_in = mqr_vbg::ColorIn{}; }
+};
+
+static int integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, int H, int W, const double* K,
+                            const double* T_wc, const uint8_t* frame_ok, float depth_scale, float depth_max,
+                            float trunc_mult, const ColorStack* color) {
     MQR_REQUIRE(v && depths && K && T_wc, "null argument");
     MQR_REQUIRE(B >= 0 && H > 0 && W > 0, "bad frame shape");
     MQR_REQUIRE(depth_loc == MQR_HOST || depth_loc == MQR_DEVICE || depth_loc == MQR_DEVICE_RESIDENT,
                 "depth_loc must be MQR_HOST, MQR_DEVICE or MQR_DEVICE_RESIDENT");
+    if (color) {
+        if (int rc = check_color_stack(v, *color, B)) return rc;
+        MQR_REQUIRE(depth_loc != MQR_DEVICE_RESIDENT, "resident frames are not supported with colour");
+    }
+    ColorInScope color_scope{v};
+    const int64_t color_frame_bytes = color ? (int64_t)color->Hc * color->Wc * 3 : 0;
     MQR_CHECK_HIP(hipSetDevice(v->device));
     // resident device frames (include/mqr.h): the caller keeps them unchanged until it synchronizes, so its
     // stream is not made to wait for this call's integrates at the return
@@ -1036,7 +1142,7 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
     if (resident) depth_loc = MQR_DEVICE;
     // device frames: both streams read them (touch, integrate) -- ordered after the caller's writes, from
     // the first batch's touch on (its frame-parameter upload and counter clear need not wait for them)
-    bool caller_ordered = depth_loc != MQR_DEVICE;
+    bool caller_ordered = depth_loc != MQR_DEVICE && !(color && color->loc == MQR_DEVICE);
     const int64_t HW = (int64_t)H * W;
     const float sdf_trunc = v->voxel_size * trunc_mult;
     const float block_size = v->voxel_size * v->R;
@@ -1057,6 +1163,7 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
         const int* idx = valid.data() + s;
         if (ensure_fp(v, b)) return 1;
         if (depth_loc != MQR_DEVICE && ensure_depth(v, b * HW)) return 1;
+        if (color && color->loc != MQR_DEVICE && ensure_color_staging(v, b * color_frame_bytes)) return 1;
         if (wait_parity_free(v, p)) return 1;
         const float* dbase = depths;
         int64_t dframe[kMaxBatch];
@@ -1075,12 +1182,40 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
             }
             dbase = v->d_depth[p];
         }
+        if (color) {
+            // the batch's colour frames (host ones staged as the depth frames are) and their parameters, on
+            // the touch stream ahead of the touch: in place before the batch's integrate is launched
+            ColorFrame* h = v->h_cfp[p];
+            for (int f = 0; f < b; ++f) {
+                const double* kc = color->K + 9 * idx[f];
+                h[f] = ColorFrame{(float)kc[0], (float)kc[4], (float)kc[2], (float)kc[5], (int64_t)idx[f]};
+            }
+            v->col_in.base = color->frames;
+            if (color->loc != MQR_DEVICE) {
+                for (int f = 0; f < b;) {
+                    int e = f + 1;
+                    while (e < b && idx[e] == idx[e - 1] + 1) ++e;
+                    MQR_CHECK_HIP(hipMemcpyAsync(v->d_color[p] + f * color_frame_bytes,
+                                                 color->frames + (int64_t)idx[f] * color_frame_bytes,
+                                                 (size_t)(color_frame_bytes * (e - f)), hipMemcpyHostToDevice,
+                                                 v->stream));
+                    for (int g = f; g < e; ++g) h[g].frame = g;
+                    f = e;
+                }
+                v->col_in.base = v->d_color[p];
+            }
+            v->col_in.Hc = color->Hc;
+            v->col_in.Wc = color->Wc;
+            MQR_CHECK_HIP(hipMemcpyAsync(v->d_cfp[p], h, sizeof(ColorFrame) * b, hipMemcpyHostToDevice, v->stream));
+        }
         const int64_t pool_before = v->pool_count;
         if (upload_frames(v, p, K, T_wc, idx, b, dframe) || reset_batch_counters(v, p)) return 1;
         // The first batch of a call: its integrate is enqueued right behind its touch, gated on the
         // device by the touch's own counters (k_gate), so the GPU does not idle while the host reads
         // them.  Later batches' counters are read while the previous integrate runs anyway.
-        const bool spec = batch == 0 && !v->probe_one && v->batch_n_max > 0;
+        // (a depth-only call on a coloured volume clears its new blocks' colours from the host-read pool count:
+        // not speculative)
+        const bool spec = batch == 0 && !v->probe_one && v->batch_n_max > 0 && !(v->has_color && !color);
         if (!caller_ordered) {
             if (order_after_caller(v->device, v->stream, v->stream2)) return 2;
             caller_ordered = true;
@@ -1142,8 +1277,8 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
         }
         if (launch_integrate(v, p, dbase, HW, H, W, b, depth_scale, depth_max, sdf_trunc, (int)pool_before)) return 1;
     }
-    if (rc == 0 && depth_loc == MQR_DEVICE) {
-        // Device frames, no error: every batch's counters have been read (pool growth, empty frames), so
+    if (rc == 0 && depth_loc == MQR_DEVICE && !(color && color->loc != MQR_DEVICE)) {
+        // Device frames (depth, and colour when given), no error: every batch's counters have been read (pool growth, empty frames), so
         // nothing is left to decide on the host -- return with the last integrate queued.  The caller's
         // stream waits for it (its next write to the frames is ordered after the library's reads); the
         // volume's next user orders behind it on the device (order_after_integrate, wait_parity_free) or
@@ -1155,6 +1290,23 @@ int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, 
     if (sync_all(v)) return 1;
     if (rc) set_error(kNoBlock);  // the prefix re-run may have overwritten the message
     return rc;
+}
+
+int mqr_integrate_frames(mqr_vbg* v, const float* depths, int depth_loc, int B, int H, int W, const double* K,
+                         const double* T_wc, const uint8_t* frame_ok, float depth_scale, float depth_max,
+                         float trunc_mult) {
+    return integrate_frames(v, depths, depth_loc, B, H, W, K, T_wc, frame_ok, depth_scale, depth_max, trunc_mult,
+                            nullptr);
+}
+
+int mqr_integrate_frames_color(mqr_vbg* v, const float* depths, int depth_loc, int B, int H, int W,
+                               const uint8_t* colors, int color_loc, int Hc, int Wc, const double* K_depth,
+                               const double* K_color, const double* T_wc, const uint8_t* frame_ok, float depth_scale,
+                               float depth_max, float trunc_mult) {
+    MQR_REQUIRE(v, "null volume");
+    const ColorStack c{colors, color_loc, Hc, Wc, K_color};
+    return integrate_frames(v, depths, depth_loc, B, H, W, K_depth, T_wc, frame_ok, depth_scale, depth_max,
+                            trunc_mult, &c);
 }
 
 int mqr_touch(mqr_vbg* v, const float* depth, int depth_loc, int H, int W, const double* K, const double* T_wc,
@@ -1204,14 +1356,33 @@ int mqr_touch(mqr_vbg* v, const float* depth, int depth_loc, int H, int W, const
     return 0;
 }
 
-int mqr_integrate(mqr_vbg* v, const int32_t* keys, int64_t n, const float* depth, int depth_loc, int H, int W,
-                  const double* K, const double* T_wc, float depth_scale, float depth_max, float trunc_mult) {
+static int integrate_keys(mqr_vbg* v, const int32_t* keys, int64_t n, const float* depth, int depth_loc, int H, int W,
+                          const double* K, const double* T_wc, float depth_scale, float depth_max, float trunc_mult,
+                          const ColorStack* color) {
     MQR_REQUIRE(v && depth && K && T_wc && (keys || n == 0), "null argument");
+    if (color)
+        if (int rc = check_color_stack(v, *color, 1)) return rc;
+    ColorInScope color_scope{v};
     MQR_CHECK_HIP(hipSetDevice(v->device));
     if (n == 0) return 0;
     if (v->wbound >= 0) v->wbound += 1;
     if (sync_all(v)) return 1;
-    if (depth_loc == MQR_DEVICE && order_after_caller(v->device, v->stream, v->stream2)) return 2;
+    if ((depth_loc == MQR_DEVICE || (color && color->loc == MQR_DEVICE)) &&
+        order_after_caller(v->device, v->stream, v->stream2))
+        return 2;
+    if (color) {
+        const int64_t bytes = (int64_t)color->Hc * color->Wc * 3;
+        v->col_in.base = color->frames;
+        if (color->loc != MQR_DEVICE) {
+            if (ensure_color_staging(v, bytes)) return 1;
+            MQR_CHECK_HIP(hipMemcpyAsync(v->d_color[0], color->frames, (size_t)bytes, hipMemcpyHostToDevice, v->stream));
+            v->col_in.base = v->d_color[0];
+        }
+        v->col_in.Hc = color->Hc;
+        v->col_in.Wc = color->Wc;
+        v->h_cfp[0][0] = ColorFrame{(float)color->K[0], (float)color->K[4], (float)color->K[2], (float)color->K[5], 0};
+        MQR_CHECK_HIP(hipMemcpyAsync(v->d_cfp[0], v->h_cfp[0], sizeof(ColorFrame), hipMemcpyHostToDevice, v->stream));
+    }
     const int64_t HW = (int64_t)H * W;
     if (ensure_table(v, v->pool_count + n)) return 1;
     const float* dptr = depth;
@@ -1240,6 +1411,20 @@ int mqr_integrate(mqr_vbg* v, const int32_t* keys, int64_t n, const float* depth
     if (sync_all(v)) rc = 1;
     MQR_CHECK_HIP(hipFree(dkeys));
     return rc;
+}
+
+int mqr_integrate(mqr_vbg* v, const int32_t* keys, int64_t n, const float* depth, int depth_loc, int H, int W,
+                  const double* K, const double* T_wc, float depth_scale, float depth_max, float trunc_mult) {
+    return integrate_keys(v, keys, n, depth, depth_loc, H, W, K, T_wc, depth_scale, depth_max, trunc_mult, nullptr);
+}
+
+int mqr_integrate_color(mqr_vbg* v, const int32_t* keys, int64_t n, const float* depth, int depth_loc, int H, int W,
+                        const uint8_t* color, int color_loc, int Hc, int Wc, const double* K_depth,
+                        const double* K_color, const double* T_wc, float depth_scale, float depth_max,
+                        float trunc_mult) {
+    MQR_REQUIRE(v, "null volume");
+    const ColorStack c{color, color_loc, Hc, Wc, K_color};
+    return integrate_keys(v, keys, n, depth, depth_loc, H, W, K_depth, T_wc, depth_scale, depth_max, trunc_mult, &c);
 }
 
 int mqr_vbg_export(mqr_vbg* v, int32_t* keys, float* tsdf, float* weight, int loc) {
@@ -1311,7 +1496,16 @@ int mqr_vbg_import(mqr_vbg* v, const int32_t* keys, const float* tsdf, const flo
         dt = ht;
         dw = hw;
     }
+    const int64_t pool_before = v->pool_count;
     int rc = activate_device_keys(v, dk, n);
+    if (!rc && v->has_color && v->pool_count > pool_before) {  // the blocks it allocated start without colour
+        const size_t block_bytes = sizeof(float) * 3 * (size_t)v->R3;
+        if (hipMemsetAsync(v->cpool + (size_t)pool_before * 3 * (size_t)v->R3, 0,
+                           block_bytes * (size_t)(v->pool_count - pool_before), v->stream) != hipSuccess) {
+            set_error("mqr_vbg_import: clearing the colours failed");
+            rc = 1;
+        }
+    }
     if (!rc) {
         hipLaunchKernelGGL(k_import, dim3((unsigned)n), dim3(256), 0, v->stream, dk, n, v->tab, v->pool, (int)v->R3,
                            dt, dw);
@@ -1326,8 +1520,63 @@ int mqr_vbg_import(mqr_vbg* v, const int32_t* keys, const float* tsdf, const flo
     return rc;
 }
 
+int mqr_vbg_export_color(mqr_vbg* v, float* colors, int loc) {
+    MQR_REQUIRE(v && colors, "null argument");
+    MQR_REQUIRE(v->has_color, "the volume carries no colour (mqr_vbg_create_color)");
+    MQR_CHECK_HIP(hipSetDevice(v->device));
+    if (sync_all(v)) return 1;
+    const int64_t n = v->pool_count;
+    if (n == 0) return 0;
+    if (loc == MQR_DEVICE && order_after_caller(v->device, v->stream)) return 2;
+    const size_t bytes = sizeof(float) * 3 * (size_t)v->R3 * (size_t)n;
+    float* dc = colors;
+    if (loc != MQR_DEVICE) MQR_CHECK_HIP(hipMalloc(&dc, bytes));
+    hipLaunchKernelGGL(k_export_color, dim3((unsigned)n), dim3(256), 0, v->stream, v->cpool, n, (int)v->R3, dc);
+    int rc = hipGetLastError() == hipSuccess ? 0 : 1;
+    if (!rc && loc != MQR_DEVICE && hipMemcpyAsync(colors, dc, bytes, hipMemcpyDeviceToHost, v->stream) != hipSuccess)
+        rc = 1;
+    if (hipStreamSynchronize(v->stream) != hipSuccess) rc = 1;
+    if (loc != MQR_DEVICE) (void)hipFree(dc);
+    if (rc) set_error("mqr_vbg_export_color: kernel or copy failed");
+    return rc;
+}
+
+int mqr_vbg_import_color(mqr_vbg* v, const int32_t* keys, const float* colors, int64_t n, int loc) {
+    MQR_REQUIRE(v && ((keys && colors) || n == 0), "null argument");
+    MQR_REQUIRE(v->has_color, "the volume carries no colour (mqr_vbg_create_color)");
+    MQR_CHECK_HIP(hipSetDevice(v->device));
+    if (n == 0) return 0;
+    if (sync_all(v)) return 1;
+    if (loc == MQR_DEVICE && order_after_caller(v->device, v->stream)) return 2;
+    const size_t bytes = sizeof(float) * 3 * (size_t)v->R3 * (size_t)n;
+    const int32_t* dk = keys;
+    const float* dc = colors;
+    int32_t* hk = nullptr;
+    float* hc = nullptr;
+    int rc = 0;
+    if (loc != MQR_DEVICE) {
+        rc = hipMalloc(&hk, sizeof(int32_t) * 3 * n) != hipSuccess || hipMalloc(&hc, bytes) != hipSuccess ||
+             hipMemcpyAsync(hk, keys, sizeof(int32_t) * 3 * n, hipMemcpyHostToDevice, v->stream) != hipSuccess ||
+             hipMemcpyAsync(hc, colors, bytes, hipMemcpyHostToDevice, v->stream) != hipSuccess;
+        dk = hk;
+        dc = hc;
+    }
+    if (!rc) {
+        // blocks the volume does not hold are skipped (colours belong to blocks mqr_vbg_import activated)
+        hipLaunchKernelGGL(k_import_color, dim3((unsigned)n), dim3(256), 0, v->stream, dk, n, v->tab, v->cpool,
+                           (int)v->R3, dc);
+        rc = hipGetLastError() != hipSuccess;
+    }
+    if (hipStreamSynchronize(v->stream) != hipSuccess) rc = 1;
+    if (hk) (void)hipFree(hk);
+    if (hc) (void)hipFree(hc);
+    if (rc) set_error("mqr_vbg_import_color: allocation, kernel or copy failed");
+    return rc ? 1 : 0;
+}
+
 int mqr_vbg_pack_weighted(mqr_vbg* v, const int32_t* union_keys, int64_t U, float* packed) {
     MQR_REQUIRE(v && (U == 0 || (union_keys && packed)), "null argument");
+    MQR_REQUIRE(!v->has_color, "mqr_vbg_pack_weighted: merging a coloured volume is not supported");
     MQR_CHECK_HIP(hipSetDevice(v->device));
     if (U == 0) return 0;
     if (sync_all(v)) return 1;
@@ -1341,6 +1590,7 @@ int mqr_vbg_pack_weighted(mqr_vbg* v, const int32_t* union_keys, int64_t U, floa
 
 int mqr_vbg_unpack_weighted(mqr_vbg* v, const int32_t* union_keys, int64_t U, const float* packed) {
     MQR_REQUIRE(v && (U == 0 || (union_keys && packed)), "null argument");
+    MQR_REQUIRE(!v->has_color, "mqr_vbg_unpack_weighted: merging a coloured volume is not supported");
     MQR_CHECK_HIP(hipSetDevice(v->device));
     if (U == 0) return 0;
     v->wbound = -1;

@@ -524,6 +524,125 @@ __global__ __launch_bounds__(NT) void k_integrate_t(const int32_t* __restrict__ 
     }
 }
 
+// ---- colour integrate -------------------------------------------------------------
+// A pass of its own, launched directly before the batch's tsdf kernel(s) with the same list, masks,
+// counters and first_new.  It reads the weights the pool holds before the batch (0 for a block the
+// batch allocated), replays integrate_column's acceptance test for every frame of the block's mask in
+// bit order -- the same float operations in the same order -- counts the weight locally, keeps the
+// voxel's three channels in registers across the frames and writes colours only.  It leaves the slot
+// mask alone: the tsdf kernel behind it still reads and clears it.  Thread tid owns the voxels
+// k NT + tid of the block (exact_block's map), so a wave reads and writes whole dwords side by side
+// in each plane of the block's [3][R^3] colours.
+template <int R, int NT>
+__global__ __launch_bounds__(NT) void k_integrate_color(
+    const int32_t* __restrict__ list, const bmask_t* __restrict__ lmask, const int* __restrict__ count,
+    int64_t list_cap, const Table t, const float2* __restrict__ pool, float* __restrict__ cpool, float voxel_size,
+    const float* __restrict__ depths, int64_t HW, int H, int W, const FrameParams* __restrict__ fps,
+    const int64_t* __restrict__ depth_frame, float depth_scale, float depth_max, float sdf_trunc, int first_new,
+    const uint8_t* __restrict__ colors, int Hc, int Wc, const ColorFrame* __restrict__ cfs) {
+    constexpr int R2 = R * R;
+    constexpr int R3 = R2 * R;
+    constexpr int ZPER = R3 / NT;   // voxels per thread
+    constexpr int ZSTEP = NT / R2;  // z stride between a thread's voxels
+    static_assert(R3 % NT == 0 && NT % R2 == 0, "NT must divide R^3 and be a multiple of R^2");
+    const int64_t n = min((int64_t)*count, list_cap);
+    const float hm1 = (float)H - 1.0f, wm1 = (float)W - 1.0f;
+    const float hcm1 = (float)Hc - 1.0f, wcm1 = (float)Wc - 1.0f;
+    const int64_t HWc = (int64_t)Hc * Wc;
+    const bool unit_scale = depth_scale == 1.0f;
+    const int tid = threadIdx.x;
+    const int xv = tid % R, yv = (tid / R) % R, z0 = tid / R2;
+    for (int64_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const int32_t slot = list[i];
+        const int buf = t.vals[slot];
+        if (buf < 0) continue;
+        const bmask_t mask = readfirstlane_mask(lmask ? lmask[i] : bm_frames(t.mask[slot]));
+        int xb, yb, zb;
+        unpack_key(t.keys[slot], xb, yb, zb);
+        const bool fresh = buf >= first_new;  // allocated by this batch: weights and colours start at 0
+        const float2* __restrict__ vox = pool + (int64_t)buf * R3;
+        float* __restrict__ col = cpool + (int64_t)buf * (3 * R3);
+        float w[ZPER], c0[ZPER], c1[ZPER], c2[ZPER], zs[ZPER];
+#pragma unroll
+        for (int k = 0; k < ZPER; ++k) {
+            const int p = k * NT + tid;
+            w[k] = fresh ? 0.f : vox[p].y;
+            c0[k] = fresh ? 0.f : col[p];
+            c1[k] = fresh ? 0.f : col[R3 + p];
+            c2[k] = fresh ? 0.f : col[2 * R3 + p];
+            zs[k] = (float)(zb * R + z0 + k * ZSTEP) * voxel_size;
+        }
+        const float xs = (float)(xb * R + xv) * voxel_size;
+        const float ys = (float)(yb * R + yv) * voxel_size;
+        uint32_t dirty = fresh ? 0xffffffffu : 0u;  // a fresh block is written whole
+        bmask_t m = mask;
+        while (m) {
+            const int f = bm_ctz(m);
+            m &= m - 1;
+            const FrameParams& fp = fps[f];
+            const ColorFrame cf = cfs[f];
+            const float* __restrict__ dep = depths + depth_frame[f] * HW;
+            const uint8_t* __restrict__ img = colors + cf.frame * HWc * 3;
+            const float ax = xs * fp.ext[0] + ys * fp.ext[1];
+            const float ay = xs * fp.ext[4] + ys * fp.ext[5];
+            const float az = xs * fp.ext[8] + ys * fp.ext[9];
+#pragma unroll
+            for (int k = 0; k < ZPER; ++k) {
+                const float xc = (ax + zs[k] * fp.ext[2]) + fp.ext[3];
+                const float yc = (ay + zs[k] * fp.ext[6]) + fp.ext[7];
+                const float zc = (az + zs[k] * fp.ext[10]) + fp.ext[11];
+                const float inv_z = rcp_rn(zc);
+                const float u = fp.fx * xc * inv_z + fp.cx;
+                const float v = fp.fy * yc * inv_z + fp.cy;
+                if (!(v >= 0 && u >= 0 && v <= hm1 && u <= wm1)) continue;
+                const float dv = dep[(int)v * W + (int)u];
+                const float d = unit_scale ? dv : div_rn(dv, depth_scale);
+                const float sdf = d - zc;
+                if (d <= 0 || d > depth_max || zc <= 0 || sdf < -sdf_trunc) continue;
+                const float wgt = w[k];
+                w[k] = wgt + 1;
+                const float uc = cf.fx * xc * inv_z + cf.cx;
+                const float vc = cf.fy * yc * inv_z + cf.cy;
+                if (!(vc >= 0 && uc >= 0 && vc <= hcm1 && uc <= wcm1)) continue;  // keeps its colour
+                const float inv_wsum = rcp_rn(wgt + 1);
+                const uint8_t* px = img + ((int64_t)(int)vc * Wc + (int)uc) * 3;
+                c0[k] = (wgt * c0[k] + (float)px[0]) * inv_wsum;
+                c1[k] = (wgt * c1[k] + (float)px[1]) * inv_wsum;
+                c2[k] = (wgt * c2[k] + (float)px[2]) * inv_wsum;
+                dirty |= 1u << k;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < ZPER; ++k)
+            if (dirty & (1u << k)) {
+                const int p = k * NT + tid;
+                col[p] = c0[k];
+                col[R3 + p] = c1[k];
+                col[2 * R3 + p] = c2[k];
+            }
+    }
+}
+
+// Colours in and out of the planar pool: [n][R^3][3] float32 outside, [buf][3][R^3] inside.
+__global__ void k_export_color(const float* __restrict__ cpool, int64_t n, int R3, float* __restrict__ out) {
+    const int64_t b = blockIdx.x;
+    if (b >= n) return;
+    for (int q = threadIdx.x; q < 3 * R3; q += blockDim.x)
+        out[b * 3 * R3 + q] = cpool[b * 3 * R3 + (int64_t)(q % 3) * R3 + q / 3];
+}
+
+__global__ void k_import_color(const int32_t* __restrict__ keys, int64_t n, const Table t, float* __restrict__ cpool,
+                               int R3, const float* __restrict__ in) {
+    const int64_t b = blockIdx.x;
+    if (b >= n) return;
+    const int64_t slot = table_find(t, pack_key(keys[3 * b], keys[3 * b + 1], keys[3 * b + 2]));
+    if (slot < 0) return;
+    const int buf = t.vals[slot];
+    if (buf < 0) return;
+    for (int q = threadIdx.x; q < 3 * R3; q += blockDim.x)
+        cpool[(int64_t)buf * 3 * R3 + (int64_t)(q % 3) * R3 + q / 3] = in[b * 3 * R3 + q];
+}
+
 // Longest-processing-time order of a batch list: counting sort by the number of the batch's frames
 // that touched each block (popcount of its slot mask), descending.  The integrate grid then ends on
 // short blocks instead of whichever long blocks the touch order happened to put last.  One

@@ -87,6 +87,36 @@ __device__ bool trilinear(const CastVol& v, BlockCache& c, float px, float py, f
     return true;
 }
 
+// Colour at world point p: the 8 lattice corners of trilinear() with its fractions, corner order
+// and seam handling; a corner contributes r c with r = (wx wy) wz when it exists and has w > 0, and the result
+// is (sum r c / sum r) / 255 per channel, 0 when the sum of r is not greater than 0.  cpool: [buf][3][R^3].
+__device__ void trilinear_color(const CastVol& v, const float* __restrict__ cpool, BlockCache& c, float px, float py,
+                                float pz, float (&out)[3]) {
+    out[0] = out[1] = out[2] = 0.0f;
+    const float gx = px / v.voxel, gy = py / v.voxel, gz = pz / v.voxel;
+    const float x0 = floorf(gx), y0 = floorf(gy), z0 = floorf(gz);
+    if (!(fabsf(x0) < 0x1p24f && fabsf(y0) < 0x1p24f && fabsf(z0) < 0x1p24f)) return;
+    const float fx = gx - x0, fy = gy - y0, fz = gz - z0;
+    const int ix = (int)x0, iy = (int)y0, iz = (int)z0;
+    float S = 0.0f, acc[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 8; ++k) {
+        const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
+        const int X = ix + dx, Y = iy + dy, Z = iz + dz;
+        const int bx = floor_div(X, v.R), by = floor_div(Y, v.R), bz = floor_div(Z, v.R);
+        const int32_t buf = block_buf(v, c, bx, by, bz);
+        if (buf < 0) continue;
+        const int64_t vi = ((Z - bz * v.R) * v.R + (Y - by * v.R)) * v.R + (X - bx * v.R);
+        if (!(v.pool[(int64_t)buf * v.R3 + vi].y > 0.0f)) continue;
+        const float wx = dx ? fx : 1.0f - fx, wy = dy ? fy : 1.0f - fy, wz = dz ? fz : 1.0f - fz;
+        const float r = (wx * wy) * wz;
+        const float* col = cpool + (int64_t)buf * 3 * v.R3 + vi;
+        S = S + r;
+        for (int ch = 0; ch < 3; ++ch) acc[ch] = acc[ch] + r * col[ch * v.R3];
+    }
+    if (S > 0.0f)
+        for (int ch = 0; ch < 3; ++ch) out[ch] = (acc[ch] / S) / 255.0f;
+}
+
 // Cell (0 .. cells - 1) ranges, then one whole-map range per frame at cells + f (the blocks with a corner
 // behind the camera: they cover every cell, so they are kept once per frame and the march folds them in).
 __global__ __launch_bounds__(256) void k_cast_range(const uint64_t* __restrict__ bkeys,
@@ -155,13 +185,16 @@ __global__ __launch_bounds__(256) void k_cast_range(const uint64_t* __restrict__
 }
 
 // 256 threads = four waves, wave w the 8 x 8 pixel tile (w % 2, w / 2) of a 16 x 16 pixel square.
+// COLOR: a coloured volume asked for its colour map (cpool, color); the instantiation without compiles none of it.
+template <bool COLOR>
 __global__ __launch_bounds__(256) void k_volume_cast(CastVol v, const FrameParams* __restrict__ fps, int H, int W,
                                                      int Hc, int Wc, int df, int64_t cells,
                                                      const uint32_t* __restrict__ rmin,
                                                      const uint32_t* __restrict__ rmax, float off, float depth_scale,
                                                      float wthr, float sdf_trunc, int refine,
                                                      float* __restrict__ depth, float* __restrict__ vertex,
-                                                     float* __restrict__ normal) {
+                                                     float* __restrict__ normal, const float* __restrict__ cpool,
+                                                     float* __restrict__ color) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
     const int y = blockIdx.y * 16 + (wave >> 1) * 8 + (lane >> 3);
@@ -262,6 +295,13 @@ __global__ __launch_bounds__(256) void k_volume_cast(CastVol v, const FrameParam
         normal[3 * pix + 1] = n[1];
         normal[3 * pix + 2] = n[2];
     }
+    if constexpr (COLOR) {
+        float c[3] = {0.f, 0.f, 0.f};
+        if (hit) trilinear_color(v, cpool, bc, hx, hy, hz, c);
+        color[3 * pix + 0] = c[0];
+        color[3 * pix + 1] = c[1];
+        color[3 * pix + 2] = c[2];
+    }
 }
 
 // The last call's device times per device (as the other *_last_ms entry points keep them), and timing events
@@ -336,18 +376,20 @@ using namespace mqr;
 
 extern "C" {
 
-int mqr_vbg_ray_cast(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int keys_loc, const double* K,
-                     const double* T_wc, int n, int H, int W, float depth_scale, float depth_min, float depth_max,
-                     float weight_threshold, float trunc_voxel_multiplier, int range_map_down_factor,
-                     float pixel_offset, int flags, float* depth, float* vertex, float* normal, int out_loc) {
+int mqr_vbg_ray_cast_color(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int keys_loc, const double* K,
+                           const double* T_wc, int n, int H, int W, float depth_scale, float depth_min,
+                           float depth_max, float weight_threshold, float trunc_voxel_multiplier,
+                           int range_map_down_factor, float pixel_offset, int flags, float* depth, float* vertex,
+                           float* normal, float* color, int out_loc) {
     MQR_REQUIRE(v && K && T_wc, "ray_cast: null argument");
+    MQR_REQUIRE(!color || v->has_color, "ray_cast: the volume carries no colour");
     MQR_REQUIRE(n > 0 && n <= 65535, "ray_cast: the frame count must be in [1, 65535], got " + std::to_string(n));
     MQR_REQUIRE(H > 0 && W > 0, "ray_cast: height and width must be positive");
     MQR_REQUIRE(range_map_down_factor > 0, "ray_cast: range_map_down_factor must be positive");
     MQR_REQUIRE(depth_min >= 0, "ray_cast: depth_min must be >= 0");  // (a NaN fails both tests)
     MQR_REQUIRE(depth_max > depth_min && std::isfinite(depth_max), "ray_cast: depth_max must be finite and > depth_min");
     MQR_REQUIRE(finite_all(K, (int64_t)n * 9) && finite_all(T_wc, (int64_t)n * 16), "ray_cast: non-finite K or T_wc");
-    MQR_REQUIRE(depth || vertex || normal, "ray_cast: all three outputs are null");
+    MQR_REQUIRE(depth || vertex || normal || color, "ray_cast: all outputs are null");
     MQR_REQUIRE(n_keys >= 0 && (n_keys == 0 || block_keys), "ray_cast: block keys missing");
     MQR_REQUIRE((keys_loc == MQR_HOST || keys_loc == MQR_DEVICE) && (out_loc == MQR_HOST || out_loc == MQR_DEVICE),
                 "ray_cast: a location must be MQR_HOST or MQR_DEVICE");
@@ -375,16 +417,18 @@ int mqr_vbg_ray_cast(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int 
     CastScratch s{};
     if (cast_scratch(v, cells, n, block_keys && !dev_keys ? n_keys : 0, s)) return 1;
     // host outputs: staged in a block of the process's device-block cache, returned at the end of the call
-    float *d_depth = depth, *d_vertex = vertex, *d_normal = normal;
+    float *d_depth = depth, *d_vertex = vertex, *d_normal = normal, *d_color = color;
     ScratchLayout O;
     const bool stage = out_loc == MQR_HOST;
     O.add(d_depth, npix, stage && depth);
     O.add(d_vertex, 3 * npix, stage && vertex);
     O.add(d_normal, 3 * npix, stage && normal);
+    O.add(d_color, 3 * npix, stage && color);
     if (!stage) {
         d_depth = depth;
         d_vertex = vertex;
         d_normal = normal;
+        d_color = color;
     }
     CastEvents tm(v->device);  // (declared before `drain`: the events go back after the stream is drained)
     if (!tm.take()) {
@@ -419,15 +463,17 @@ int mqr_vbg_ray_cast(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int 
         MQR_CHECK_HIP(hipGetLastError());
     }
     MQR_CHECK_HIP(hipEventRecord(tm.ev[1], st));
-    hipLaunchKernelGGL(k_volume_cast, dim3((unsigned)((W + 15) / 16), (unsigned)tiles_y, (unsigned)n), dim3(256), 0, st,
-                       cv, s.fp, H, W, Hc, Wc, df, cells, s.rmin, s.rmax, pixel_offset, depth_scale, weight_threshold,
-                       sdf_trunc, flags & MQR_CAST_REFINE, d_depth, d_vertex, d_normal);
+    hipLaunchKernelGGL(color ? k_volume_cast<true> : k_volume_cast<false>,
+                       dim3((unsigned)((W + 15) / 16), (unsigned)tiles_y, (unsigned)n), dim3(256), 0, st, cv, s.fp, H, W,
+                       Hc, Wc, df, cells, s.rmin, s.rmax, pixel_offset, depth_scale, weight_threshold, sdf_trunc,
+                       flags & MQR_CAST_REFINE, d_depth, d_vertex, d_normal, (const float*)v->cpool, d_color);
     MQR_CHECK_HIP(hipGetLastError());
     MQR_CHECK_HIP(hipEventRecord(tm.ev[2], st));
     if (stage) {
         if (depth && copy_to_host(v->device, depth, d_depth, sizeof(float) * (size_t)npix, st)) return 1;
         if (vertex && copy_to_host(v->device, vertex, d_vertex, sizeof(float) * 3 * (size_t)npix, st)) return 1;
         if (normal && copy_to_host(v->device, normal, d_normal, sizeof(float) * 3 * (size_t)npix, st)) return 1;
+        if (color && copy_to_host(v->device, color, d_color, sizeof(float) * 3 * (size_t)npix, st)) return 1;
     }
     MQR_CHECK_HIP(hipStreamSynchronize(st));
     // the outputs are complete: a failed time query loses the times, not the call
@@ -440,6 +486,15 @@ int mqr_vbg_ray_cast(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int 
     g_times[v->device].range_ms = r;
     g_times[v->device].march_ms = m;
     return 0;
+}
+
+int mqr_vbg_ray_cast(mqr_vbg* v, const int32_t* block_keys, int64_t n_keys, int keys_loc, const double* K,
+                     const double* T_wc, int n, int H, int W, float depth_scale, float depth_min, float depth_max,
+                     float weight_threshold, float trunc_voxel_multiplier, int range_map_down_factor,
+                     float pixel_offset, int flags, float* depth, float* vertex, float* normal, int out_loc) {
+    return mqr_vbg_ray_cast_color(v, block_keys, n_keys, keys_loc, K, T_wc, n, H, W, depth_scale, depth_min, depth_max,
+                                  weight_threshold, trunc_voxel_multiplier, range_map_down_factor, pixel_offset, flags,
+                                  depth, vertex, normal, nullptr, out_loc);
 }
 
 int mqr_vbg_ray_cast_last_ms(mqr_vbg* v, double* range_ms, double* march_ms) {

@@ -51,6 +51,9 @@ SIGNATURES = {
     "mqr_device_synchronize": (ctypes.c_int, [ctypes.c_int]),
     "mqr_device_mem_info": (ctypes.c_int, [ctypes.c_int, _i64p, _i64p]),
     "mqr_vbg_create": (ctypes.c_int, [ctypes.c_float, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(_vp)]),
+    "mqr_vbg_create_color": (ctypes.c_int, [ctypes.c_float, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                            ctypes.POINTER(_vp)]),
+    "mqr_vbg_has_color": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_int)]),
     "mqr_vbg_destroy": (ctypes.c_int, [_vp]),
     "mqr_vbg_reset": (ctypes.c_int, [_vp]),
     "mqr_vbg_size": (ctypes.c_int, [_vp, _i64p]),
@@ -62,6 +65,14 @@ SIGNATURES = {
                                      _f64p, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
     "mqr_integrate_frames": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p,
                                             _f64p, _u8p, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
+    "mqr_integrate_color": (ctypes.c_int, [_vp, _i32p, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _f64p, _f64p,
+                                           ctypes.c_float, ctypes.c_float, ctypes.c_float]),
+    "mqr_integrate_frames_color": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                  _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _f64p, _f64p, _f64p,
+                                                  _u8p, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
+    "mqr_vbg_export_color": (ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    "mqr_vbg_import_color": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int]),
     "mqr_vbg_export": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int]),
     "mqr_vbg_import": (ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int]),
     "mqr_vbg_pack_weighted": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp]),
@@ -168,6 +179,10 @@ SIGNATURES = {
                                         ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                         ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_int,
                                         _vp, _vp, _vp, ctypes.c_int]),
+    "mqr_vbg_ray_cast_color": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _f64p, _f64p, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                              ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                              ctypes.c_float, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "mqr_vbg_ray_cast_last_ms": (ctypes.c_int, [_vp, _f64p, _f64p]),
     "mqr_vbg_profile": (ctypes.c_int, [_vp, ctypes.c_int]),
     "mqr_vbg_set_variant": (ctypes.c_int, [_vp, ctypes.c_int]),
@@ -294,6 +309,8 @@ def load(path: str = LIB_PATH):
 # complete before the library reads them.
 ORDERED = frozenset({
     "mqr_touch", "mqr_integrate", "mqr_integrate_frames", "mqr_vbg_export", "mqr_vbg_import",
+    "mqr_integrate_color", "mqr_integrate_frames_color", "mqr_vbg_export_color", "mqr_vbg_import_color",
+    "mqr_vbg_ray_cast_color",
     "mqr_vbg_pack_weighted", "mqr_vbg_unpack_weighted", "mqr_xchg_create", "mqr_xchg_send_segment",
     "mqr_xchg_recv_segment", "mqr_geom_copy", "mqr_confidence", "mqr_confidence_counts", "mqr_decode_depth", "mqr_decode_depth_masked",
     "mqr_decode_color_frames",

@@ -121,7 +121,8 @@ class DeviceGeom:
                 Tensor(DeviceArray(self, t, (self.nt, 3), np.int32, self.device_id)))
 
     def colors(self):
-        """The result's vertex colours as a Tensor over HBM, or None (every producer but the mesh simplification)."""
+        """The result's vertex colours as a Tensor over HBM, or None (made by the extraction of a coloured volume
+        and by the simplification of a coloured mesh)."""
         from . import _lib
         c = ctypes.c_void_p()
         _lib.call("mqr_geom_device_colors", self._h, ctypes.byref(c))
@@ -513,7 +514,7 @@ class PointCloud:
     @classmethod
     def from_device(cls, geom: DeviceGeom, device=None):
         p, n, _ = geom.tensors()
-        return cls(p, n, device=device)
+        return cls(p, n, device=device, colors=geom.colors())
 
     @property
     def points(self):
@@ -586,7 +587,11 @@ class TriangleMesh:
 
     @classmethod
     def from_device(cls, geom: DeviceGeom, device=None):
-        return cls(*geom.tensors(), device=device)
+        mesh = cls(*geom.tensors(), device=device)
+        c = geom.colors()
+        if c is not None:
+            mesh.vertex["colors"] = c
+        return mesh
 
     @property
     def vertices(self):
